@@ -1,9 +1,21 @@
 #!/usr/bin/env python3
 """Headline benchmark: Msamples/s of the path-tracing hot path (BASELINE.json
 metric) on BASELINE config 2 — SphereGrid (scenes/sphere_grid.rs, the
-reference's random-spheres scene) at 1920x1080x1024spp, max depth 50 — plus,
-in the same invocation, north_star's target scene (config 4's 1M-triangle
-binary PLY mesh, `mesh_ply`) as `config.secondary`.
+reference's random-spheres scene) at 1920x1080x1024spp, max depth 50.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only that: it
+builds and uploads the scene, runs W warmup and N timed steps, and prints the
+result line (headline value, ms_per_step, and the roofline of those same
+steps). `--dump-outputs DIR` also writes the image the last timed step left
+— what a caller of the timed path reads back — as DIR/rgb.npy (float32 colour
+sums, H x W x 3), DIR/bounces.npy (float64 bounce sums, H x W) and
+DIR/passes.npy; the scene and the sample streams are fixed by the arguments,
+so two builds run with the same arguments can be compared array for array.
+`--full` adds, in the same invocation, everything else described below:
+north_star's target scene (config 4's 1M-triangle binary PLY mesh,
+`mesh_ply`) as `config.secondary`, the CPU baselines, BASELINE configs 1, 3
+and 5, every workload on the other walk, the drop-in call pattern and, with
+N > 1 GPUs, the gather check (each still has its own --no-... switch).
 
 A step = one pass of the hot path over one batch: `--spp-per-step` (default
 1024) samples of every pixel of the 1920x1080 frame, i.e. the whole
@@ -131,6 +143,11 @@ def parse():
     ap.add_argument("--pmc-json", default=None, help="PMC summary (default profiles/pmc_<scene>.json)")
     ap.add_argument("--no-dropin", action="store_true", help="skip the drop-in render() call-pattern runs")
     ap.add_argument("--dropin-batch", type=int, default=256, help="1-spp passes per mrt_image_render call")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the secondary scene, CPU baselines, config 1/3/5 "
+                         "lines, the other walk, the drop-in call pattern, the N>1 gather check")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the image the last timed step left (rgb, bounces, passes) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -444,6 +461,15 @@ class MultiRunner:
         _, b, passes = self.img.read()
         return float(b.astype("float64").sum()) / (self.W * self.H * max(passes, 1))
 
+    def outputs(self):
+        """What the caller of step() holds after the last one: the image's
+        colour sums, bounce sums and pass count (mrt_image_read)."""
+        import numpy as np
+
+        rgb, b, passes = self.img.read()
+        return {"rgb": rgb.reshape(self.H, self.W, 3), "bounces": b.reshape(self.H, self.W).astype(np.float64),
+                "passes": np.array([passes], dtype=np.float64)}
+
     def close(self):
         self.img.close()
         self.ctx.close()
@@ -497,6 +523,15 @@ class RankRunner:
     def mean_bounces(self):
         spp = self.frame.spp
         return float(self.frame.frame()[1].double().sum().item()) / (self.W * self.H * max(spp, 1))
+
+    def outputs(self):
+        """Rank 0's gathered frame after the last step, as MultiRunner.outputs."""
+        import numpy as np
+
+        rgb, b = self.frame.frame()
+        return {"rgb": rgb.float().cpu().numpy().reshape(self.H, self.W, 3),
+                "bounces": b.double().cpu().numpy().reshape(self.H, self.W),
+                "passes": np.array([self.frame.spp], dtype=np.float64)}
 
     def close(self):
         self.frame.close()
@@ -703,9 +738,10 @@ def roofline_for(a, scene, cnt, ks, samples_total, elapsed, n_gpus, plan, trav: 
 
 
 def run_scene(a, scene: str, steps: int, warmup: int, rank: int, world: int, dev, cpu: bool, devices=None,
-              spp=None, width=None, height=None) -> dict:
+              spp=None, width=None, height=None, dump=None) -> dict:
     """Bench one scene: `warmup` untimed steps (the first counts traversal
-    events for the algorithmic-bytes model), then `steps` timed steps."""
+    events for the algorithmic-bytes model), then `steps` timed steps; `dump`:
+    the directory rank 0 writes the last step's outputs to (--dump-outputs)."""
     import copy
 
     a = copy.copy(a)
@@ -756,12 +792,13 @@ def run_scene(a, scene: str, steps: int, warmup: int, rank: int, world: int, dev
                              "ms_per_step": round(g_ms / steps, 3),
                              "device_render_ms_per_step": [round(x / steps, 3) for x in r.device_ms()],
                              "per_rank_ms_per_step": [round(e / steps * 1e3, 3) for e in per_rank]}
-            try:
-                out["gather"]["check"] = verify_gather(a, r, scene, devices)
-                out["gather"]["identical"] = out["gather"]["check"]["identical"]
-            except Exception as e:  # a failed check must not hide the timed number
-                out["gather"]["check"] = {"identical": None, "error": str(e)}
-                out["gather"]["identical"] = None
+            if a.full:
+                try:
+                    out["gather"]["check"] = verify_gather(a, r, scene, devices)
+                    out["gather"]["identical"] = out["gather"]["check"]["identical"]
+                except Exception as e:  # a failed check must not hide the timed number
+                    out["gather"]["check"] = {"identical": None, "error": str(e)}
+                    out["gather"]["identical"] = None
         else:
             out["gather"] = {"path": "one process per GPU: mrt_render_device + torch.distributed gather",
                              "transport": "RCCL (dist.gather over xGMI)" if a.dist_backend == "nccl" else
@@ -771,6 +808,12 @@ def run_scene(a, scene: str, steps: int, warmup: int, rank: int, world: int, dev
     if rank == 0:
         out["mean_bounces_per_sample"] = round(r.mean_bounces(), 4)
         out["mrays_per_s"] = round(value * roof["segments_per_sample"], 1) if roof else None
+        if dump:
+            import numpy as np
+
+            Path(dump).mkdir(parents=True, exist_ok=True)
+            for name, arr in r.outputs().items():
+                np.save(Path(dump) / f"{name}.npy", arr)
     r.close()
     if cpu:
         try:
@@ -885,7 +928,8 @@ def main():
     multi = a.mode == "multi"
     devices = device_list(a) if multi else None
     n_gpus = len(devices) if multi else world
-    secondary = a.secondary if (a.secondary and a.secondary != "none" and a.secondary != a.scene) else None
+    # a plain run times the headline scene only; everything else is --full's
+    secondary = a.secondary if (a.full and a.secondary and a.secondary != "none" and a.secondary != a.scene) else None
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         # multi mode: the launcher's other ranks only join barriers (gloo, no GPU)
@@ -903,13 +947,13 @@ def main():
             torch.cuda.set_device(0 if multi else (local % torch.cuda.device_count() if world > 1 else 0))
     dev = torch.device("cuda", torch.cuda.current_device())
     solo = n_gpus == 1 and world == 1
-    cpu = rank == 0 and solo and not a.no_cpu_baseline
+    cpu = a.full and rank == 0 and solo and not a.no_cpu_baseline
 
-    head = run_scene(a, a.scene, a.steps, a.warmup, rank, world, dev, cpu, devices)
+    head = run_scene(a, a.scene, a.steps, a.warmup, rank, world, dev, cpu, devices, dump=a.dump_outputs)
     sec = run_scene(a, secondary, a.secondary_steps, 1, rank, world, dev, cpu, devices) if secondary else None
 
     dropin, c1, configs = None, None, None
-    if rank == 0 and solo and not a.no_dropin:
+    if a.full and rank == 0 and solo and not a.no_dropin:
         dropin = {}
         for sc, ref in ((a.scene, head["value"]), (secondary, sec["value"] if sec else None)):
             if sc:
@@ -918,7 +962,7 @@ def main():
                 except Exception as e:
                     dropin[sc] = {"error": str(e)}
     walks = None
-    if rank == 0 and solo and not a.no_configs:
+    if a.full and rank == 0 and solo and not a.no_configs:
         configs = config_lines(a, rank, world, dev, devices)
         walks = other_walk_lines(a, rank, world, dev, devices,
                                  {"headline": head, "secondary": sec, "c3": configs.get("c3")})

@@ -74,6 +74,13 @@ def test_rehearsal_devices():
         bench.device_list(_args("--gpus", "2", "--devices", "0"))
 
 
+def test_plain_run_is_the_default_and_full_is_a_flag():
+    a = _args("--gpus", "1", "--steps", "5", "--warmup", "2")
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 5, 2)
+    a = _args("--full", "--dump-outputs", "some/dir")
+    assert a.full is True and a.dump_outputs == "some/dir"
+
+
 def test_context_options_from_flags():
     assert bench.context_options(_args("--opt", "queues=1", "--opt", "trace_chunk=256")) == \
         {"queues": 1, "trace_chunk": 256}

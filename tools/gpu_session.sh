@@ -4,7 +4,7 @@
 # failure (fault, abort, time limit) ends the session — no step is retried.
 #
 #   bash tools/gpu_session.sh tests                 # pytest -m gpu + smoke
-#   bash tools/gpu_session.sh bench [bench args]    # the default bench line (+ args)
+#   bash tools/gpu_session.sh bench [bench args]    # the plain bench line (+ args); `bench --full`: the whole line
 #   bash tools/gpu_session.sh profile SCENE...      # rocprofv3 stats + stamped PMC (tools/profile.sh)
 #   bash tools/gpu_session.sh configs               # every BASELINE config scene, timing only
 #   LABELS="a b" LIBS="x.so y.so" bash tools/gpu_session.sh ab   # bench per library build (MASSRT_LIB)
@@ -76,7 +76,7 @@ case $MODE in
       done
     done <<< "$ARGSETS" ;;
   rehearse)  # N=2 on the 1-GPU box: one process, one context over devices {0,0}, peer-copy gather
-    timeout -k 10 600 python -u bench.py --gpus 2 --devices 0,0 --steps 2 --secondary none --no-cpu-baseline \
+    timeout -k 10 600 python -u bench.py --full --gpus 2 --devices 0,0 --steps 2 --secondary none --no-cpu-baseline \
       --no-dropin --no-configs > gpurun_out/session/rehearse2.log 2>&1 &&
     tail -1 gpurun_out/session/rehearse2.log | cut -c1-600 ;;
   *) echo "unknown mode $MODE"; exit 2 ;;
