@@ -1,0 +1,190 @@
+// ctx.h — the single-device context behind the C ABI (include/massrt.h) and
+// the host functions that trace.hip, render.hip, passes.hip and api.hip
+// share. Not part of the C ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <array>
+#include <atomic>
+#include <map>
+#include <string>
+#include <tuple>
+#include <utility>
+#include <vector>
+
+#include "../../../include/massrt.h"
+#include "../host/options.h"
+#include "frames.h"
+#include "pool.h"
+
+struct HipError {
+  std::string msg;
+};
+#define HIP_CHECK(x)                                                                      \
+  do {                                                                                    \
+    hipError_t e_ = (x);                                                                  \
+    if (e_ != hipSuccess) throw HipError{std::string(#x) + ": " + hipGetErrorString(e_)}; \
+  } while (0)
+
+struct ApiError {
+  int code;
+  std::string msg;
+};
+
+// One independent path pool driven on its own stream. Several queues share
+// the work counter and run concurrently, so one queue's k_trace tail (the
+// last long rays on few lanes) overlaps the other queues' kernels instead of
+// idling the GPU.
+struct Queue {
+  hipStream_t stream = nullptr;
+  PathBufs bufs[2]{};
+  uint4* hits = nullptr;
+  size_t cap = 0;
+  Ctrl* ctrl = nullptr;        // device
+  HostStatus* h_stat = nullptr;  // pinned coherent, 2 slots, written by k_status (lagged status reads)
+  HostStatus* d_stat = nullptr;  // the same memory as the device addresses it
+  hipEvent_t ev[2]{};
+  hipEvent_t join = nullptr;
+};
+
+struct mrt_ctx {
+  int device = 0;
+  MultiDev* multi = nullptr;  // a context over several devices (frames.hip): the rest is unused
+  std::atomic<int> images{0};  // live mrt_image objects created on this handle (any thread)
+  hipStream_t stream = nullptr;
+  std::string err;
+  // scene
+  void* scene_mem = nullptr;
+  size_t scene_bytes = 0;
+  mrt::DevScene S{};
+  bool has_scene = false;
+  mrt::DevCamera cam{};
+  bool has_camera = false;
+  // options: the values set (mrt_set_option; kOptDefs), what the rules know
+  // about the scene, and everything derived from the two (apply_options)
+  int64_t opt[mrt::kNumOpts];
+  mrt::SceneFacts facts;
+  mrt::Tuning tun{};
+  bool scene_alpha = true;  // the scene has alpha-tested triangles
+  bool scene_ext = false;   // composite surfaces or a CubeMap background (the EXT kernel variants)
+  // render state
+  size_t pool_cap = 0;  // paths over all queues
+  void* pool_mem = nullptr;
+  Queue q[mrt::kMaxQueues];
+  uint32_t* work = nullptr;    // shared work counter of the wavefront loop (word 1: tonemap max count)
+  uint32_t* gamma_d = nullptr; // display: gamma byte thresholds (256 words)
+  float4* results = nullptr;  // the results slab (results_cap samples)
+  size_t results_cap = 0;
+  // acc_done: recorded on the caller's stream after the accumulate that read
+  // the results slab (and after any other caller-stream work on the shared
+  // buffers, mark_ctx_busy); the next render's queues fork after it.
+  // (Round 2's two alternating queue sets, measured 5-12% slower, are in
+  // profiles/r3_experiments/ab_branches.patch.)
+  hipEvent_t acc_done = nullptr;
+  hipEvent_t set_fork = nullptr;
+  // kernel-timing marks resolved lazily (mrt_get_kernel_stats): a timed
+  // render does not wait for its set's drain
+  std::vector<std::array<hipEvent_t, 3>> pend_marks;
+  std::vector<std::array<hipEvent_t, 2>> pend_fin;
+  mrt::DevCounters* d_cnt = nullptr;
+  uint32_t* dbg = nullptr;  // MRT_DEBUG_BOUNDS record (4 words)
+  int cus = 1;
+  uint32_t trace_grid = 1024;   // k_trace_simple workgroups (cus * 4)
+  uint32_t refill_grid = 2048;  // k_refill workgroups (grid-stride; cus * 8)
+  std::map<std::pair<const void*, size_t>, uint32_t> grids;  // persistent grid per (kernel, LDS bytes)
+  // k_render: per-lane current world ray; event pair timing one launch
+  float4* slot_ro = nullptr;
+  float4* slot_rd = nullptr;
+  size_t slots_cap = 0;
+  hipEvent_t tev[2] = {nullptr, nullptr};
+
+  std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>, std::pair<uint32_t*, uint32_t>> pixlists;
+  // host-buffer render staging
+  float* d_acc_rgb = nullptr;
+  uint32_t* d_acc_b = nullptr;
+  size_t acc_cap = 0;
+  // kernel timing
+  std::vector<hipEvent_t> ev_pool;
+  size_t ev_used = 0;
+  mrt_kernel_stats kstats{};
+  // device ray buffer for mrt_trace_rays
+  float* d_rays = nullptr;
+  uint4* d_rhits = nullptr;
+  size_t rays_cap = 0;
+};
+
+// errors without a context (api.hip); not exported from the library
+__attribute__((visibility("hidden"))) extern thread_local std::string mrt_global_error;
+
+// Runs f on the context's device; exceptions become the context's error text
+// and an MRT_ERR_* code.
+template <typename F>
+int guarded(mrt_ctx* c, F&& f) {
+  if (!c) {
+    mrt_global_error = "null context";
+    return MRT_ERR_INVALID;
+  }
+  try {
+    HIP_CHECK(hipSetDevice(c->device));
+    f();
+    c->err.clear();
+    return MRT_OK;
+  } catch (const ApiError& e) {
+    c->err = e.msg;
+    return e.code;
+  } catch (const HipError& e) {
+    c->err = e.msg;
+    return MRT_ERR_HIP;
+  } catch (const std::bad_alloc&) {
+    c->err = "out of host memory";
+    return MRT_ERR_NOMEM;
+  } catch (const std::exception& e) {
+    c->err = e.what();
+    return MRT_ERR_INVALID;
+  }
+}
+
+// A multi-device handle (mrt_create_multi): entry points that act on one
+// device run on device 0; scene and camera go to every device.
+template <typename F>
+int on_dev0(mrt_ctx* c, F&& f) {
+  mrt_ctx* d = multi_dev(c->multi, 0);
+  const int rc = f(d);
+  c->err = d->err;
+  return rc;
+}
+template <typename F>
+int on_each(mrt_ctx* c, F&& f) {
+  for (int i = 0; i < multi_count(c->multi); ++i) {
+    mrt_ctx* d = multi_dev(c->multi, i);
+    const int rc = f(d);
+    if (rc != MRT_OK) {
+      c->err = d->err;
+      return rc;
+    }
+  }
+  c->err.clear();
+  return MRT_OK;
+}
+#define MRT_DEV0(c, call) \
+  if ((c) && (c)->multi) return on_dev0((c), [&](mrt_ctx* c) { return call; })
+#define MRT_EACH(c, call) \
+  if ((c) && (c)->multi) return on_each((c), [&](mrt_ctx* c) { return call; })
+
+// ---- trace.hip ----
+// k_trace over pool buffer `in` of queue `q`, specialised on the scene, on stream `st`
+void launch_trace(mrt_ctx* c, hipStream_t st, const Queue& q, const PathBufs& in, uint32_t cur, bool count,
+                  float tmin, float tmax);
+void launch_trace_simple(mrt_ctx* c, const Queue& q, uint32_t cur);  // MRT_RENDER_SIMPLE_TRACE, on the queue's stream
+uint32_t persistent_grid(mrt_ctx* c, const void* f, size_t smem, bool shared = false, int block = kBlock,
+                         int share_num = 3, int share_den = 4);
+
+// ---- render.hip ----
+void wait_queues(mrt_ctx* c, hipStream_t st);
+void ensure_pool(mrt_ctx* c, size_t P);
+void ensure_slots(mrt_ctx* c, size_t n);
+std::vector<uint32_t> shard_pixel_list(uint32_t W, uint32_t H, uint32_t si, uint32_t sc);
+std::pair<uint32_t*, uint32_t> pixlist(mrt_ctx* c, uint32_t W, uint32_t H, uint32_t si, uint32_t sc);
+void mark_ctx_busy(mrt_ctx* c, hipStream_t st);
+void render_device(mrt_ctx* c, const mrt_render_args* a, float* d_rgb, uint32_t* d_b, hipStream_t st);
+void resolve_kernel_timing(mrt_ctx* c);

@@ -1,5 +1,5 @@
-// frames.h — internal interface between render.hip (the single-device
-// context) and frames.hip (a context over several devices, the
+// frames.h — internal interface between the single-device context (ctx.h,
+// api.hip) and frames.hip (a context over several devices, the
 // device-resident Image). Not part of the C ABI.
 #pragma once
 #include <stdint.h>
@@ -21,7 +21,7 @@ int multi_set_gather(MultiDev* m, int64_t mode, std::string& err);
 int64_t multi_gather(const MultiDev* m);
 const char* multi_transport(const MultiDev* m);
 
-// ---- render.hip ----
+// ---- api.hip ----
 mrt_ctx* ctx_wrap_multi(MultiDev* m);  // the public handle of a multi-device context
 MultiDev* ctx_multi(const mrt_ctx* c);  // null for a single-device context
 void ctx_set_error(mrt_ctx* c, const std::string& msg);

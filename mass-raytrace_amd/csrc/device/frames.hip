@@ -14,8 +14,8 @@
 //
 // This file uses only the public single-device entry points on the
 // per-device contexts (mrt_render_device, mrt_shard_pack/unpack_device,
-// mrt_prepass_device, mrt_tonemap_device); render.hip routes the entry
-// points of a multi-device handle here (frames.h).
+// mrt_prepass_device, mrt_tonemap_device); the single-device entry points
+// route a multi-device handle here (ctx.h MRT_DEV0 / MRT_EACH, frames.h).
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -34,7 +34,7 @@
 
 #include "frames.h"
 
-int massrt_ctx_device(const mrt_ctx* ctx);  // render.hip
+int massrt_ctx_device(const mrt_ctx* ctx);  // api.hip
 
 namespace {
 
@@ -380,7 +380,7 @@ int guard(mrt_ctx* ctx, F&& f) {
 
 }  // namespace
 
-// ---- render.hip's side of a multi-device handle (frames.h) -----------------
+// ---- the context's side of a multi-device handle (frames.h) -----------------
 int multi_count(const MultiDev* m) { return (int)m->devs.size(); }
 mrt_ctx* multi_dev(const MultiDev* m, int i) { return m->devs[(size_t)i]; }
 

@@ -684,7 +684,7 @@ struct Builder {
     }
   }
 
-  // the per-scene rule's verdict before building (render.hip apply_options):
+  // the per-scene rule's verdict before building (options.h derive_tuning):
   // the reference walk for a generic-triangle term or a big instanced world
   // (round 6: generic triangles no longer decline it — the normal cones and
   // the wild instances' own tests made mesh_ply's near-first walk the faster)

@@ -379,7 +379,7 @@ struct Hit {
 };
 
 // World::intersect over the preorder stream, one record per step so that a
-// persistent kernel can interleave many rays per lane (render.hip k_trace).
+// persistent kernel can interleave many rays per lane (trace.hip k_trace).
 // Each lane's sequence of box/primitive tests is exactly the reference's
 // (left-first recursion with shrinking t_max, geom.rs:185-205); only which
 // lanes of a wave are busy at a time differs.

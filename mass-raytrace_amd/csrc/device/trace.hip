@@ -1,0 +1,385 @@
+// trace.hip — the closest hit of every active ray of a path pool
+// (World::intersect): the persistent k_trace, the choice among its variants,
+// its launch, and mrt_trace_rays, which sends arbitrary rays through it.
+#include <string.h>
+
+#include <algorithm>
+
+#include "ctx.h"
+
+using namespace mrt;
+
+namespace {
+
+// Persistent closest-hit kernel: a fixed grid of waves pulls chunks of rays
+// from a counter; inside a wave a lane whose ray has finished takes the next
+// ray of the wave's chunk as soon as enough lanes are idle, so the SIMD keeps
+// issuing for busy lanes instead of waiting for the wave's slowest ray.
+//
+// LDS=true: the scene's treelet (layout.h, upload.cpp build_treelet) is first
+// copied into the workgroup's LDS; records with an LDS-tagged index are then
+// read there (ds_read_b128) instead of through L1/L2 — the top of the trees,
+// which every ray visits, and small instanced BLAS whole. BLK threads per
+// workgroup share one copy.
+constexpr size_t kTraceLdsMaxBytes = 160 * 1024;
+constexpr uint32_t kStashQuads = 4;  // float4s per lane of the world-ray stash (TravIn::stash)
+
+// RNG: the scene's traversal draws random numbers (Volume, Mix alpha tests):
+// each ray carries its path stream through the traversal and stores it back.
+// (R > 1 would interleave R rays per lane — software ILP; measured slower at
+// its 84 VGPRs, so only R = 1 is instantiated.)
+// NF: the verified near-first walk (path.h trav_*_nf): the SAH trees walked
+// near child first with a per-lane stack in LDS (kNfStack x BLK words of
+// dynamic shared memory), the winner checked against the reference tree,
+// rays that fail the check walked again the reference's way.
+template <bool COUNT, bool LDS, uint32_t ALPHA, bool RNG, int BLK, bool NF = false>
+__global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(NF ? (COUNT ? 1 : 5) : (ALPHA == 0 && !RNG && !COUNT ? 8 : 1)))) void k_trace(DevScene S, PathBufs in, uint4* hits, Ctrl* ctrl, uint32_t cur,
+                                                  DevCounters* cnt, float tmin, float tmax, TraceTune tune) {
+  static_assert(!NF || (!LDS && !RNG), "the near-first walk has no treelet and no traversal draws");
+  constexpr int R = 1;
+  const uint32_t n = ctrl->active[cur];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    ctrl->active[cur ^ 1] = 0;
+    ctrl->surv[cur ^ 1] = 0;
+  }
+  if (n == 0) return;  // uniform: every workgroup reads the same n
+  if (LDS) {
+    for (uint32_t k = threadIdx.x; k < S.n_tlet; k += BLK) mrt_lds[k] = reinterpret_cast<const uint4*>(S.tlet)[k];
+    __syncthreads();
+  }
+  TravIn tin_{S, reinterpret_cast<const uint4*>(LDS ? S.slots_tl : S.slots), LDS ? S.tl_world_begin : S.world_begin,
+              in.ro, in.rd, tmin, in.rng, tmax};
+  if (!LDS && !NF) {  // the reference walk without a treelet: LDS holds the world-ray stash (TravIn::stash)
+    tin_.stash = reinterpret_cast<float4*>(mrt_lds) + threadIdx.x;
+    tin_.stash_stride = (uint32_t)BLK;
+  }
+  const TravIn& tin = tin_;
+  const NfStack stk{reinterpret_cast<uint32_t*>(mrt_lds) + threadIdx.x, (uint32_t)BLK};
+  LocalCounters lc;
+  uint32_t seg = 0, nh = 0;
+  uint32_t pool = 0, pool_end = 0;  // wave-uniform chunk [pool, pool_end)
+  bool drained = false;             // wave-uniform: every group's share is taken
+  // XCD-aware ray ranges: the pool is roughly in pixel order (camera rays in
+  // tile order, survivors compacted in order), so giving each XCD group a
+  // contiguous eighth keeps an XCD's rays — and the scene parts they touch —
+  // together in that XCD's L2. A group whose eighth is taken helps the next.
+  uint32_t grp = blockIdx.x % kGroups, visited = 0;  // wave-uniform
+  Trav t[R];
+#pragma unroll
+  for (int q = 0; q < R; ++q) {
+    t[q] = Trav{};  // fully initialised: idle lanes must not carry undefined state
+    t[q].done = true;
+    t[q].ray = kIdle;
+  }
+  for (;;) {
+    unsigned long long idle[R];
+    uint32_t n_idle = 0;
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+      idle[q] = __ballot(t[q].ray == kIdle);
+      n_idle += (uint32_t)__popcll(idle[q]);
+    }
+    if (n_idle >= tune.refill * R || n_idle == 64u * R) {
+      while (pool == pool_end && !drained) {  // grab the next chunk (wave-uniform)
+        const uint32_t lo = (uint32_t)((uint64_t)n * grp / kGroups), hi = (uint32_t)((uint64_t)n * (grp + 1) / kGroups);
+        uint32_t b = 0;
+        if (lane_id() == 0) b = atomicAdd(&ctrl->group_next[grp * 32], tune.chunk);
+        b = __shfl(b, 0, 64);
+        if (b < hi - lo) {
+          pool = lo + b;
+          pool_end = hi - pool > tune.chunk ? pool + tune.chunk : hi;
+        } else if (++visited == kGroups) {
+          drained = true;
+        } else {
+          grp = (grp + 1) % kGroups;
+        }
+      }
+      const uint32_t avail = pool_end - pool;
+      uint32_t off = 0;
+      unsigned long long live = 0;
+#pragma unroll
+      for (int q = 0; q < R; ++q) {
+        if (t[q].ray == kIdle) {
+          const uint32_t r = off + lane_rank(idle[q]);
+          if (r < avail) trav_init<RNG, LDS>(tin, t[q], MRT_IDX(S, pool + r, n, 20), tmax, NF ? S.nf_world : 0xFFFFFFFFu);
+        }
+        off += (uint32_t)__popcll(idle[q]);
+        live |= __ballot(t[q].ray != kIdle);
+      }
+      pool += n_idle < avail ? n_idle : avail;
+      if (live == 0) break;  // chunk source exhausted
+    }
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+      // box run: keep stepping boxes with little per-step overhead while at
+      // least tune.box_min lanes are at one (lanes reaching a primitive wait)
+      // Two steps per loop iteration: with one, the compiler carried the
+      // record just loaded into the loop-header registers with 8 v_mov per
+      // step; unrolled, the two steps alternate register sets and the copies
+      // are gone (sphere_grid 671 -> 703, cube_field 254 -> 266, mesh_ply
+      // 740 -> 749 Msamples/s, same box).
+      auto box_step = [&]() {  // false: too few lanes at a box
+        // a done lane holds an END record (or an idle lane's zeros), never a
+        // box, so the record's flag alone decides (no done mask in the ballot)
+        const bool run_box = trav_at_box(t[q]);
+        const unsigned long long bm = __builtin_amdgcn_ballot_w64(run_box);
+        if ((uint32_t)__popcll(bm) < tune.box_min) return false;
+        if (run_box) {
+          if (NF && t[q].sp != kExactMode)
+            trav_box_index_nf<COUNT>(tin, stk, t[q], lc);
+          else
+            trav_box_index<COUNT>(tin, t[q], lc);
+        }
+        if (run_box && (!NF || t[q].sp != kNfDone)) trav_fetch<LDS>(tin, t[q]);
+        if (COUNT) {
+          lc.wave_slots += lane_id() == 0 ? 64u : 0u;
+          lc.lane_steps += run_box ? 1u : 0u;
+        }
+        return true;
+      };
+      while (box_step() && box_step()) {
+      }
+      // idle lanes hold a done Trav; a near-first lane whose walk is over
+      // waits for the check below.
+      // One step per busy lane (a box, or a primitive once enough lanes wait
+      // at one or no lane is at a box), then ONE record fetch for every lane
+      // that moved: the address unit costs per wave instruction, so the box
+      // and primitive lanes share the load pair instead of issuing one each.
+      // Primitive run (the box run's mirror): while at least tune.prim_run
+      // lanes are at a primitive, they step alone (a leaf's primitives one
+      // after another) instead of paying the box branch beside each step —
+      // the same code with the box lanes masked off, so nothing is inlined
+      // twice. Every pass steps a lane: while the run is on, tune.prim_run >=
+      // tune.prim_batch (options.h derive_tuning), so its lanes have prim_go.
+      for (;;) {
+        const bool busy = !t[q].done && (!NF || t[q].sp != kNfDone);
+        const bool at_box = busy && trav_at_box(t[q]);
+        const unsigned long long box_mask = __ballot(at_box);
+        const unsigned long long prim_mask = __ballot(busy && !at_box);
+        // (the near-first walk only: the reference walk's k_trace, compiled
+        // with this loop, lost 14% — 971 -> 832 on sphere_grid at any
+        // threshold, profiles/r6_primrun/ — so there it folds to one step)
+        const bool prim_run = NF && (uint32_t)__popcll(prim_mask) >= tune.prim_run;  // wave-uniform
+        const bool box_go = at_box && !prim_run;
+        const bool prim_go = (__popcll(prim_mask) >= tune.prim_batch || box_mask == 0) && busy && !at_box;
+        if (box_go) {
+          if (NF && t[q].sp != kExactMode)
+            trav_box_index_nf<COUNT>(tin, stk, t[q], lc);
+          else
+            trav_box_index<COUNT>(tin, t[q], lc);
+        }
+        if (prim_go) {
+          if (NF && t[q].sp != kExactMode)
+            trav_prim_index_nf<COUNT, ALPHA>(tin, stk, t[q], lc);
+          else
+            trav_prim_index<COUNT, ALPHA, RNG, LDS>(tin, t[q], lc);
+        }
+        if ((box_go || prim_go) && !t[q].done && (!NF || t[q].sp != kNfDone)) trav_fetch<LDS>(tin, t[q]);
+        if (COUNT) {
+          lc.wave_slots += lane_id() == 0 ? 64u : 0u;
+          lc.lane_steps += (box_go || prim_go) ? 1u : 0u;
+        }
+        if (!prim_run) break;
+      }
+      // near-first walks that are over: check their hits (done, or the
+      // reference's walk from the start) — batched: the check is a few
+      // hundred wave instructions, so finished lanes wait (holding an END
+      // record) until tune.nf_batch of them can share one pass, or until no
+      // lane is walking any more
+      if (NF) {
+        const bool over = t[q].sp == kNfDone;
+        const unsigned long long om = __builtin_amdgcn_ballot_w64(over);
+        if (om != 0 && ((uint32_t)__popcll(om) >= tune.nf_batch ||
+                        __builtin_amdgcn_ballot_w64(!t[q].done && !over) == 0) && over) {
+          nf_finish<COUNT>(tin, t[q], lc);
+          if (!t[q].done) trav_fetch<LDS>(tin, t[q]);
+        }
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+      if (t[q].ray != kIdle && t[q].done) {
+        if (RNG) trav_store_rng(tin, t[q]);
+        const Hit h = trav_hit<LDS>(tin, t[q]);
+        hits[t[q].ray] = make_uint4(__float_as_uint(h.t), h.prim, h.container, 0u);
+        seg += 1;
+        nh += t[q].prim != kRefNone;
+        t[q].ray = kIdle;
+      }
+    }
+  }
+  if (COUNT) flush_counters(cnt, lc, seg, nh, 0, 0);
+}
+
+// Debug/bisection variant (MRT_RENDER_SIMPLE_TRACE): one ray per thread,
+// the whole traversal in closest_hit.
+template <bool RNG>
+__global__ __launch_bounds__(kBlock) void k_trace_simple(DevScene S, PathBufs in, uint4* hits, Ctrl* ctrl,
+                                                         uint32_t cur, DevCounters* cnt) {
+  const uint32_t n = ctrl->active[cur];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    ctrl->active[cur ^ 1] = 0;
+    ctrl->surv[cur ^ 1] = 0;
+  }
+  LocalCounters lc;
+  uint32_t seg = 0, nh = 0;
+  const TravIn tin{S, reinterpret_cast<const uint4*>(S.slots), S.world_begin, in.ro, in.rd, kTmin, in.rng};
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+    PathRng rng{0, 0};
+    if (RNG) {
+      const uint4 q = in.rng[i];
+      rng = PathRng{(unsigned long long)q.x | ((unsigned long long)q.y << 32),
+                    (unsigned long long)q.z | ((unsigned long long)q.w << 32)};
+    }
+    Hit h = closest_hit<true, RNG>(tin, i, INFINITY, lc, rng);
+    if (RNG)
+      in.rng[i] = make_uint4((uint32_t)rng.s0, (uint32_t)(rng.s0 >> 32), (uint32_t)rng.s1, (uint32_t)(rng.s1 >> 32));
+    hits[i] = make_uint4(__float_as_uint(h.t), h.prim, h.container, 0u);
+    seg += 1;
+    nh += h.prim != kRefNone;
+  }
+  flush_counters(cnt, lc, seg, nh, 0, 0);
+}
+
+// mrt_trace_rays: arbitrary rays go through the product k_trace. In: rays
+// (6 floats each) -> pool slots; out: hit records -> mrt_hit with front_face.
+__global__ __launch_bounds__(kBlock) void k_rays_in(const float* rays, uint32_t n, PathBufs out) {
+  uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const float* r = rays + 6 * (size_t)i;
+  out.ro[i] = make_float4(r[0], r[1], r[2], __uint_as_float(i));
+  out.rd[i] = make_float4(r[3], r[4], r[5], __uint_as_float(0u));
+  const PathRng g = path_rng(0, i, 0xFFFFFFFEu);  // traversal draws of mrt_trace_rays (massrt.h)
+  out.rng[i] = make_uint4((uint32_t)g.s0, (uint32_t)(g.s0 >> 32), (uint32_t)g.s1, (uint32_t)(g.s1 >> 32));
+}
+
+__global__ __launch_bounds__(kBlock) void k_rays_out(DevScene S, PathBufs in, const uint4* hits, uint32_t n,
+                                                     uint4* out) {
+  uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const float4 o4 = in.ro[i], d4 = in.rd[i];
+  const uint4 hv = hits[i];
+  Hit h{__uint_as_float(hv.x), hv.y, hv.z};
+  uint32_t front = 0;
+  if (h.prim != kRefNone)
+    front = resolve_hit(S, V3{o4.x, o4.y, o4.z}, V3{d4.x, d4.y, d4.z}, h).front_face ? 1u : 0u;
+  out[i] = make_uint4(h.prim, h.container, __float_as_uint(h.prim != kRefNone ? h.t : 0.0f), front);
+}
+
+// The k_trace variant for a scene: counting or not; the record stream's top
+// in LDS (a treelet, with the workgroup size that shares it); alpha tests
+// none / plain surfaces / composite surfaces (EXT); traversal draws; or the
+// near-first walk (scenes with NF trees, no treelet, no traversal draws).
+using TraceFn = void (*)(DevScene, PathBufs, uint4*, Ctrl*, uint32_t, DevCounters*, float, float, TraceTune);
+template <bool COUNT, uint32_t ALPHA, bool RNG>
+TraceFn trace_kernel_lds(int block) {
+  return block == 1024  ? k_trace<COUNT, true, ALPHA, RNG, 1024>
+         : block == 512 ? k_trace<COUNT, true, ALPHA, RNG, 512>
+                        : k_trace<COUNT, true, ALPHA, RNG, kBlock>;
+}
+template <bool COUNT, uint32_t ALPHA>
+TraceFn trace_kernel_a(bool lds, bool rng, int block, bool nf) {
+  if (nf) return k_trace<COUNT, false, ALPHA, false, kBlock, true>;
+  if (lds) return rng ? trace_kernel_lds<COUNT, ALPHA, true>(block) : trace_kernel_lds<COUNT, ALPHA, false>(block);
+  return rng ? k_trace<COUNT, false, ALPHA, true, kBlock> : k_trace<COUNT, false, ALPHA, false, kBlock>;
+}
+template <bool COUNT>
+TraceFn trace_kernel_c(bool lds, uint32_t alpha, bool rng, int block, bool nf) {
+  return alpha == 2   ? trace_kernel_a<COUNT, 2>(lds, rng, block, nf)
+         : alpha == 1 ? trace_kernel_a<COUNT, 1>(lds, rng, block, nf)
+                      : trace_kernel_a<COUNT, 0>(lds, rng, block, nf);
+}
+TraceFn trace_kernel(bool count, bool lds, uint32_t alpha, bool rng, int block, bool nf) {
+  return count ? trace_kernel_c<true>(lds, alpha, rng, block, nf) : trace_kernel_c<false>(lds, alpha, rng, block, nf);
+}
+
+}  // namespace
+
+// Occupancy-sized persistent grid for kernel f with `smem` dynamic LDS.
+// `shared`: the kernel runs beside the other queues' kernels (k_trace with
+// several queues) — it takes 3/4 of the occupancy, so another queue's trace
+// and shade launches find room on every CU instead of queueing behind a
+// grid that holds the whole GPU until its last ray (sphere_grid, 2 queues:
+// 8 WGs/CU 585, 6 WGs/CU 618 Msamples/s).
+uint32_t persistent_grid(mrt_ctx* c, const void* f, size_t smem, bool shared, int block, int share_num,
+                         int share_den) {
+  auto key = std::make_pair(f, smem);
+  auto it = c->grids.find(key);
+  if (it != c->grids.end()) return it->second;
+  if (smem > 0) HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTraceLdsMaxBytes));
+  int per_cu = 0;
+  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, block, smem));
+  if (shared) per_cu = std::max(1, per_cu * share_num / share_den);
+  if (c->tun.wgs_per_cu) per_cu = (int)c->tun.wgs_per_cu;
+  const uint32_t g = (uint32_t)c->cus * (uint32_t)std::max(1, per_cu);
+  c->grids[key] = g;
+  return g;
+}
+
+void launch_trace(mrt_ctx* c, hipStream_t st, const Queue& q, const PathBufs& in, uint32_t cur, bool count,
+                  float tmin, float tmax) {
+  const Tuning& t = c->tun;
+  const bool nf = t.use_nf, lds = !nf && c->facts.treelet;
+  const uint32_t alpha = c->scene_alpha ? (c->scene_ext ? 2u : 1u) : 0u;
+  const int block = lds ? t.trace_block : kBlock;
+  const TraceFn f = trace_kernel(count, lds, alpha, c->facts.trav_rng, block, nf);
+  // dynamic LDS: the near-first stack (kNfStack words per lane), the treelet, or the world-ray stash (4 x 16 B per lane)
+  const size_t smem = nf ? (size_t)kNfStack * block * 4 : lds ? (size_t)c->S.n_tlet * 16 : (size_t)kStashQuads * block * 16;
+  // Near-first: kNfStack KiB of LDS per workgroup allow 6 waves per SIMD, its
+  // registers (<= 128 VGPRs: the rounding margins' state and code, round 5,
+  // would spill at 80) at least 4. Beside another queue the walk takes 3
+  // WG/CU: its vector-memory unit is the shared limit, so more of its waves
+  // buy nothing while k_shade beside it gains (profiles/r4_nf/tune.txt §6:
+  // 4 -> 3 WG/CU +0.8%, 2 WG/CU -14%)
+  uint32_t grid = persistent_grid(c, (const void*)f, smem, t.queues > 1, block, nf ? 1 : 3, nf ? 1 : 4);
+  const uint32_t nf_cap = 3u * (uint32_t)c->cus;
+  if (nf && t.queues > 1 && !t.wgs_per_cu && grid > nf_cap) grid = c->grids[std::make_pair((const void*)f, smem)] = nf_cap;
+  hipLaunchKernelGGL(f, dim3(grid), dim3(block), smem, st, c->S, in, q.hits, q.ctrl, cur, c->d_cnt, tmin, tmax, t.trace);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_trace_simple(mrt_ctx* c, const Queue& q, uint32_t cur) {
+  auto* f = c->facts.trav_rng ? k_trace_simple<true> : k_trace_simple<false>;
+  hipLaunchKernelGGL(f, dim3(c->trace_grid), dim3(kBlock), 0, q.stream, c->S, q.bufs[cur], q.hits, q.ctrl, cur, c->d_cnt);
+  HIP_CHECK(hipGetLastError());
+}
+
+extern "C" int mrt_trace_rays(mrt_ctx* c, const float* rays, uint32_t n, float t_min, float t_max, mrt_hit* out) {
+  MRT_DEV0(c, mrt_trace_rays(c, rays, n, t_min, t_max, out));
+  return guarded(c, [&] {
+    if (!c->has_scene) throw ApiError{MRT_ERR_STATE, "no scene uploaded"};
+    if (n == 0) return;
+    if (!rays || !out) throw ApiError{MRT_ERR_INVALID, "null argument"};
+    if (n > c->rays_cap) {
+      hipFree(c->d_rays);
+      hipFree(c->d_rhits);
+      c->d_rays = nullptr;
+      c->d_rhits = nullptr;
+      HIP_CHECK(hipMalloc(&c->d_rays, (size_t)n * 24));
+      HIP_CHECK(hipMalloc(&c->d_rhits, (size_t)n * 16));
+      c->rays_cap = n;
+    }
+    HIP_CHECK(hipMemcpyAsync(c->d_rays, rays, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
+    wait_queues(c, c->stream);
+    ensure_pool(c, (size_t)n * c->tun.queues);  // all rays go to queue 0
+    const Queue& q = c->q[0];
+    const uint32_t g = (n + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_rays_in, dim3(g), dim3(kBlock), 0, c->stream, (const float*)c->d_rays, n, q.bufs[0]);
+    HIP_CHECK(hipGetLastError());
+    Ctrl init{{n, 0}, n, 0};
+    HIP_CHECK(hipMemcpyAsync(q.ctrl, &init, sizeof(Ctrl), hipMemcpyHostToDevice, c->stream));
+    launch_trace(c, c->stream, q, q.bufs[0], 0u, true, t_min, t_max);
+    hipLaunchKernelGGL(k_rays_out, dim3(g), dim3(kBlock), 0, c->stream, c->S, q.bufs[0], (const uint4*)q.hits, n,
+                       c->d_rhits);
+    HIP_CHECK(hipGetLastError());
+    std::vector<uint4> h(n);
+    HIP_CHECK(hipMemcpyAsync(h.data(), c->d_rhits, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < n; ++i) {
+      out[i].prim = h[i].x;
+      out[i].container = h[i].y;
+      memcpy(&out[i].t, &h[i].z, 4);
+      out[i].front_face = h[i].w;
+    }
+  });
+}

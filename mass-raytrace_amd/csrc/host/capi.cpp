@@ -8,7 +8,7 @@
 #include "display.h"
 #include "world.h"
 
-// device ordinal of a context (render.hip), -1 for a null context
+// device ordinal of a context (api.hip), -1 for a null context
 int massrt_ctx_device(const mrt_ctx* ctx);
 
 using namespace massrt;

@@ -143,19 +143,23 @@ def test_prim_run_is_bit_identical(scene, golden_dir, traversal):
     -1: the per-walk default).
     Only the order of the lanes' steps changes, never a lane's own walk, so
     the image and the work counted are the same bit for bit (the reference
-    walk's kernel has no primitive run: the option changes nothing there)."""
+    walk's kernel has no primitive run: the option changes nothing there).
+    Near-first, a primitive batch of 48 with the default run: the run starts
+    no sooner than the batch (options.h derive_tuning; tests/test_options.py),
+    so every pass of the run loop steps a lane."""
+    cases = [{"trace_prim_run": p} for p in (65, 1, 32, -1)] + ([{"trace_prim_batch": 48}] if traversal == 1 else [])
     for src in (scene, massrt.Builder(1).builtin("cube_field", ASPECT, golden_dir),
                 massrt.Builder(1).builtin("cornell", ASPECT, golden_dir)):
         out, cnt = [], []
-        for p in (65, 1, 32, -1):
-            c = massrt.Context(0, options={"trace_prim_run": p, "traversal": traversal})
+        for opts in cases:
+            c = massrt.Context(0, options={**opts, "traversal": traversal})
             c.upload(src)
             out.append(c.render(W, H, 0, 16, seed=21))
             c.reset_counters()
             c.render(W, H, 0, 2, seed=21, counters=True)
             cnt.append(c.counters())
             c.close()
-        for j in (1, 2, 3):
+        for j in range(1, len(cases)):
             assert _same(out[0][0], out[j][0]) and _same(out[0][1], out[j][1]), j
             for k in ("samples", "segments", "bounces", "shaded", "closest_hits", "triangle_tests", "sphere_tests"):
                 assert cnt[0][k] == cnt[j][k], (j, k)

@@ -328,7 +328,7 @@ def test_tiny_coordinates_keep_the_early_decision(ctx):
 @pytest.mark.parametrize("scene", ["sphere_grid", "cube_field"])
 def test_drain_handoff_is_bit_identical(small_scenes, scene):
     """A queue whose work is exhausted hands its last paths to the fused
-    kernel in adopt mode (render.hip launch_finish_v): the image must be
+    kernel in adopt mode (render.hip launch_finish): the image must be
     the per-bounce wavefront's bit for bit — never, at once, by default
     (option finish_paths)."""
     b, _ = small_scenes[scene]
