@@ -225,14 +225,12 @@ int mrt_upload_scene(mrt_ctx* c, const mrt_scene_desc* d) {
     up(o_bgf, hs.bg_faces.data(), hs.bg_faces.size() * sizeof(GpuSurfRef));
     up(o_bgm, hs.bg_m, sizeof(hs.bg_m));
     up(o_vnf, hs.vnf_leaf.data(), hs.vnf_leaf.size() * 4);
-    DevScene S{};
+    DevScene S = host_dev_scene(hs);  // sizes and flags; its pointers now go to the device copies
     S.slots = (const uint32_t*)(base + o_slots);
     S.slots_tl = (const uint32_t*)(base + o_stl);
     S.tlet = (const uint32_t*)(base + o_tlet);
     S.n_tlet = (uint32_t)(hs.tlet.size() / 4);
     S.tl_world_begin = hs.tl_world_begin;
-    S.world_begin = hs.world_begin;
-    S.world_end = hs.world_end;
     S.inst_inv = (const float*)(base + o_inv);
     S.inst_fwd = (const float*)(base + o_fwd);
     S.inst_mat = (const uint32_t*)(base + o_imat);
@@ -243,32 +241,14 @@ int mrt_upload_scene(mrt_ctx* c, const mrt_scene_desc* d) {
     S.materials = (const GpuMaterial*)(base + o_mat);
     S.textures = (const GpuTexture*)(base + o_tex);
     S.texels = (const uint32_t*)(base + o_texel);
-    S.fast_ok = (hs.fast_ok ? 1u : 0u) | (hs.early_ok ? 2u : 0u);
     S.vol_nid = (const float*)(base + o_vnid);
     S.vol_mat = (const uint32_t*)(base + o_vmat);
     S.ln_table = ln_table.empty() ? nullptr : (const float*)(base + o_ln);
-    S.n_vol = (uint32_t)hs.vol_nid.size();
-    S.n_slots = (uint32_t)(hs.slots.size() / 4);
-    S.n_tris = (uint32_t)(hs.tri_shade.size() / (kTriShadeQuads * 4));
-    S.n_sph = (uint32_t)hs.sph_mat.size();
-    S.n_inst = (uint32_t)hs.inst_mat.size();
-    S.n_models = (uint32_t)hs.model_mat.size();
-    S.n_materials = (uint32_t)hs.materials.size();
-    S.n_textures = (uint32_t)hs.textures.size();
-    S.n_texels = (uint32_t)hs.texels.size();
     S.dbg = c->dbg;
-    S.bg_kind = hs.bg_kind;
-    for (int k = 0; k < 4; ++k) S.bg_color[k] = hs.bg_color[k];
     S.surf_ops = (const GpuSurfOp*)(base + o_sops);
-    S.n_surf_ops = (uint32_t)hs.surf_ops.size();
     S.bg_faces = (const GpuSurfRef*)(base + o_bgf);
     S.bg_m = (const float*)(base + o_bgm);
-    S.nf_ok = hs.nf_ok ? 1u : 0u;
-    S.nf_world = hs.nf_world;
     S.vnf_leaf = (const uint32_t*)(base + o_vnf);
-    for (int k = 0; k < 4; ++k) S.vnf_base[k] = hs.vnf_base[k];
-    S.n_vnf = (uint32_t)(hs.vnf_leaf.size() / 2);
-    S.nfb = hs.nfb;
     c->S = S;
     c->scene_bytes = off;
     // the reference stream's size decides the per-scene rules (the NF trees follow it)

@@ -47,14 +47,14 @@ constexpr uint32_t kBoxFlag = 0x80000000u;  // slot1.w of a box: kBoxFlag | hit 
 // record" stays inside the copy; other primitives are never copied.
 constexpr uint32_t kLdsTag = 0x40000000u;
 constexpr uint32_t kIdxMask = 0x3FFFFFFFu;
-// the region being traversed has ended (record after its last one; path.h)
+// the region being traversed has ended (record after its last one; walk.h)
 constexpr uint32_t KIND_END = 0;
 enum : uint32_t { TRI_FLAG_ALPHA = 1u, TRI_FLAG_UV = 2u };  // tri_shade flags
 // a TRI record's slot1.z: the triangle id, bit 31 = the triangle is alpha-tested
 constexpr uint32_t kTriAlpha = 0x80000000u;
 constexpr uint32_t kTriIdMask = 0x0FFFFFFFu;
 
-// ---- verified near-first trees (round 4, nf_tree.cpp, path.h trav_*_nf) ----
+// ---- verified near-first trees (round 4, nf_tree.cpp, walk_nf.h trav_*_nf) ----
 // A second set of trees over the same primitives, appended to the slot
 // array after the reference stream: a surface-area-heuristic BVH over the
 // world's objects (spheres, instances, models, world triangles) and one per
@@ -170,8 +170,8 @@ struct DevScene {
   const GpuMaterial* materials;
   const GpuTexture* textures;
   const uint32_t* texels;  // RGBA8 packed little-endian
-  uint32_t fast_ok;  // bit 0: every box coordinate in {0} U [2^-40, 2^28] (path.h qfast exact test);
-                     // bit 1: every box coordinate finite, |c| <= 2^28 (path.h early slab decision)
+  uint32_t fast_ok;  // bit 0: every box coordinate in {0} U [2^-40, 2^28] (isect.h qfast exact test);
+                     // bit 1: every box coordinate finite, |c| <= 2^28 (isect.h early slab decision)
   // array sizes (checked only in MRT_DEBUG_BOUNDS builds) and the debug record
   uint32_t n_slots, n_tris, n_sph, n_inst, n_models, n_materials, n_textures, n_texels;
   uint32_t* dbg;  // {first failing check code, index, bound, failures}

@@ -1,8 +1,8 @@
 // nf_bound.h — how far outside its own box a primitive's COMPUTED hit point
 // can lie, as a margin the near-first walk's box tests add (DESIGN.md §4,
-// "Why the near-first walk is exact"). Shared by the device walk (path.h), the
-// host tree builder that derives the constants (nf_tree.cpp) and the host
-// restatement that checks them (tools/slab_check.cpp).
+// "Why the near-first walk is exact"). Shared by the walk (walk_nf.h), the host
+// tree builder that derives the constants (nf_tree.cpp) and the host driver
+// that runs the walk and checks them in double precision (tools/slab_check.cpp).
 //
 // The walk culls a box when the ray's slab interval [t0, t1] misses
 // [tmin, cull(best)]. That is safe for a primitive P inside the box if P's
@@ -49,7 +49,7 @@ struct NfBound {
   float kc;
   // a node's cone is evaluated only while some lane of the wave has a generic
   // term rg t above this (2^-6 of the median generic triangle's extent): a
-  // bounce ray's short reach leaves the worst-case term small (path.h
+  // bounce ray's short reach leaves the worst-case term small (walk_nf.h
   // trav_box_index_nf; either value is a valid rho)
   float kcmin;
 };

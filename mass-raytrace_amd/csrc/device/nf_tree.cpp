@@ -74,7 +74,7 @@ struct Box {
 // Outward padding of an NF box plane (culling must never drop what the
 // object's own test would hit): relative 2^-22 (two ulps) plus rel_extra,
 // at least 2^-39, and never into (0, 2^-40) — the slab test's fast domain
-// (path.h coord_ok) stays intact.
+// (isect.h coord_ok) stays intact.
 float pad(float v, float dir, float rel_extra) {
   if (!(fabsf(v) < INFINITY)) return v;
   float p = v + dir * fmaxf(fabsf(v) * (0x1p-22f + rel_extra), 0x1p-39f);
@@ -104,7 +104,7 @@ float f_up(double v) {
 double norm3(const double v[3]) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }
 
 // A triangle's bound on how far its computed hit X = o + t d can lie from the
-// triangle (Triangle::intersect, geom.rs:504-533, as path.h tri_hit computes
+// triangle (Triangle::intersect, geom.rs:504-533, as isect.h tri_hit computes
 // it): |X - tri| <= a(|d|) L + pad with L = |X - o| and a(|d|) = a0 + a1 |d|;
 // pad (proportional to the triangle's size) is added to its box on the host.
 // k1: generic kappa per unit |d| (the walk requires k1 |d| <= kNfKappaMax).
@@ -393,7 +393,7 @@ struct Builder {
       case KIND_INST:
       case KIND_MODEL:
         w[4 * at + 2] = next;
-        w[4 * (at + 1)] = s.vnf_leaf[2 * (size_t)vnf_slot(r)];  // its reference world parent (path.h nf_finish)
+        w[4 * (at + 1)] = s.vnf_leaf[2 * (size_t)vnf_slot(r)];  // its reference world parent (walk_nf.h nf_finish)
         patches.push_back({at, w[4 * r + 1]});  // the reference BLAS region it enters
         if (wild_term.count(r)) wild_at.push_back({at, r});
         break;

@@ -9,7 +9,7 @@ using namespace mrt;
 
 namespace {
 
-// div_cr (path.h) against the IEEE division on random bit patterns plus
+// div_cr (isect.h) against the IEEE division on random bit patterns plus
 // structured operands (all-ones / power-of-two mantissas, range edges).
 __global__ __launch_bounds__(kBlock) void k_selftest_division(unsigned long long n, unsigned long long seed,
                                                               unsigned long long* mismatches) {
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(kBlock) void k_selftest_division(unsigned long long
     float a = __uint_as_float(ua), b = __uint_as_float(ub);
     float q;
     if ((r2 & 7) >= 5) {
-      // the slab test's fast domain (path.h TRay::fast): a = m - o with m, o in
+      // the slab test's fast domain (isect.h TRay): a = m - o with m, o in
       // {0} U [2^-40, 2^28], |b| in [2^-20, 2^20]; q = qfast(a, b, RN(1/b))
       auto coord = [](uint32_t bits, uint32_t sel) {
         uint32_t e = 87u + (sel % 68u);  // 2^-40 .. 2^27

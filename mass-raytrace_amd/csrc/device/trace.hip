@@ -28,7 +28,7 @@ constexpr uint32_t kStashQuads = 4;  // float4s per lane of the world-ray stash 
 // each ray carries its path stream through the traversal and stores it back.
 // (R > 1 would interleave R rays per lane — software ILP; measured slower at
 // its 84 VGPRs, so only R = 1 is instantiated.)
-// NF: the verified near-first walk (path.h trav_*_nf): the SAH trees walked
+// NF: the verified near-first walk (walk_nf.h trav_*_nf): the SAH trees walked
 // near child first with a per-lane stack in LDS (kNfStack x BLK words of
 // dynamic shared memory), the winner checked against the reference tree,
 // rays that fail the check walked again the reference's way.

@@ -328,7 +328,7 @@ void box_children(const std::vector<uint32_t>& w, uint32_t i, std::vector<uint32
 // mesh_ply k_trace 9.40 -> 8.95 ms, 681 -> 716 Msamples/s).
 // The world region keeps its preorder layout: an instance or model record
 // returns to the record after it (its return index is also the handle of the
-// hit's container, path.h trav_hit). Placing each instance right before its
+// hit's container, walk.h trav_hit). Placing each instance right before its
 // preorder successor instead was measured (round 3): sphere_grid and
 // cube_field unchanged, Menger 38.1 -> 31.4 Msamples/s (the instance pairs of
 // its leaves end up beside their successors' groups, not their parents').

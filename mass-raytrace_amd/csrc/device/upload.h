@@ -72,6 +72,53 @@ struct HostScene {
 
 enum { kNfBuildNever = 0, kNfBuildAlways = 1, kNfBuildAuto = 2 };
 
+// The kernel-visible scene over the HostScene's own vectors (no treelet, no
+// debug record): what the walk's host callers pass to the device headers'
+// functions (tools/slab_check.cpp; valid while `s` lives unchanged), and what
+// mrt_upload_scene starts from before it points the arrays at the device copies.
+inline DevScene host_dev_scene(const HostScene& s) {
+  DevScene S{};
+  S.slots = s.slots.data();
+  S.world_begin = s.world_begin;
+  S.world_end = s.world_end;
+  S.inst_inv = s.inst_inv.data();
+  S.inst_fwd = s.inst_fwd.data();
+  S.inst_mat = s.inst_mat.data();
+  S.model_mat = s.model_mat.data();
+  S.sph = s.sph.data();
+  S.sph_mat = s.sph_mat.data();
+  S.tri_shade = s.tri_shade.data();
+  S.materials = s.materials.data();
+  S.textures = s.textures.data();
+  S.texels = s.texels.data();
+  S.fast_ok = (s.fast_ok ? 1u : 0u) | (s.early_ok ? 2u : 0u);
+  S.n_slots = (uint32_t)(s.slots.size() / 4);
+  S.n_tris = (uint32_t)(s.tri_shade.size() / (kTriShadeQuads * 4));
+  S.n_sph = (uint32_t)s.sph_mat.size();
+  S.n_inst = (uint32_t)s.inst_mat.size();
+  S.n_models = (uint32_t)s.model_mat.size();
+  S.n_materials = (uint32_t)s.materials.size();
+  S.n_textures = (uint32_t)s.textures.size();
+  S.n_texels = (uint32_t)s.texels.size();
+  S.vol_nid = s.vol_nid.data();
+  S.vol_mat = s.vol_mat.data();
+  S.ln_table = s.ln_table.empty() ? nullptr : s.ln_table.data();
+  S.n_vol = (uint32_t)s.vol_nid.size();
+  S.surf_ops = s.surf_ops.data();
+  S.n_surf_ops = (uint32_t)s.surf_ops.size();
+  S.bg_kind = s.bg_kind;
+  for (int k = 0; k < 4; ++k) S.bg_color[k] = s.bg_color[k];
+  S.bg_faces = s.bg_faces.data();
+  S.bg_m = s.bg_m;
+  S.nf_ok = s.nf_ok ? 1u : 0u;
+  S.nf_world = s.nf_world;
+  S.vnf_leaf = s.vnf_leaf.data();
+  for (int k = 0; k < 4; ++k) S.vnf_base[k] = s.vnf_base[k];
+  S.n_vnf = (uint32_t)(s.vnf_leaf.size() / 2);
+  S.nfb = s.nfb;
+  return S;
+}
+
 // Builds the verified near-first trees of a linearised scene (after
 // build_host_scene; layout.h). A scene whose traversal draws random numbers,
 // or whose trees would need more than kNfStack stack entries, gets none
@@ -80,7 +127,7 @@ bool build_nf_trees(const mrt_scene_desc& d, HostScene& s, std::string& err);
 
 // Validates the description and linearises it. Returns false with `err` set.
 // sibling_layout=false keeps every region in plain preorder (the layout
-// before round 2; tools/slab_check.cpp checks both walk alike)
+// before round 2; tools/slab_check.cpp runs the walk over both: they walk alike)
 bool build_host_scene(const mrt_scene_desc& d, HostScene& out, std::string& err, bool sibling_layout = true);
 
 // Chooses the records copied into LDS by every k_trace workgroup (at most

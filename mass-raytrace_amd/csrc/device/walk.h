@@ -1,0 +1,342 @@
+// walk.h — the reference's walk, one record per step: the per-lane state, the
+// record loads, the box and primitive steps over the preorder stream
+// (layout.h), the whole traversal of one ray.
+//   World::intersect      world.rs:131-144
+//   BvhNode::intersect    geom.rs:185-205 (via the preorder stream, layout.h)
+//   Instance::intersect   geom.rs:403-420
+//   Volume::intersect     geom.rs:609-653
+#pragma once
+#include "isect.h"
+
+namespace mrt {
+
+struct Hit {
+  float t;
+  uint32_t prim;       // make_ref(kind, id) or kRefNone
+  uint32_t container;  // make_ref(INSTANCE|MODEL, id) or kRefNone
+};
+
+// World::intersect over the preorder stream, one record per step so that a
+// persistent kernel can interleave many rays per lane (trace.hip k_trace).
+// Each lane's sequence of box/primitive tests is exactly the reference's
+// (left-first recursion with shrinking t_max, geom.rs:185-205); only which
+// lanes of a wave are busy at a time differs.
+//
+// Register budget: the per-lane state is kept small (occupancy is the lever
+// for this latency-bound loop). The world ray is not kept: the rays live in
+// the pool buffers (ro/rd), and leaving an instance's BLAS reloads it. The
+// closest t so far is `best` (Hit.t is filled in by trav_hit()).
+struct TravIn {
+  const DevScene& S;
+  const uint4* slots;      // record stream in global memory (S.slots, or S.slots_tl beside an LDS treelet)
+  uint32_t world_begin;    // first record of the world region (an LDS-tagged index beside a treelet)
+  const float4* ro;        // ray origins  (xyz) of the pool
+  const float4* rd;        // ray directions (xyz)
+  float tmin;
+  uint4* rng = nullptr;    // the rays' RNG states (traversal draws: Volume, Mix alpha tests)
+  float tmax0 = INFINITY;  // the walk's initial t_max (a near-first lane that falls back restarts with it)
+  // k_trace (reference walk, no treelet): this lane's 4 x 16 B of LDS, stride
+  // `stash_stride` float4s, holding the world ray while the lane is inside an
+  // instance's BLAS — leaving it then costs 4 LDS reads instead of 2 pool
+  // loads and make_tray's four correctly rounded divisions (nullptr: recompute)
+  float4* stash = nullptr;
+  uint32_t stash_stride = 0;
+};
+MRT_HD void tray_stash(const TravIn& in, const TRay& r) {
+  float4* p = in.stash;
+  const uint32_t k = in.stash_stride;
+  p[0] = make_float4(r.o.x, r.o.y, r.o.z, r.d.x);
+  p[k] = make_float4(r.d.y, r.d.z, r.yx, r.yy);
+  p[2 * k] = make_float4(r.yz, r.oyx, r.oyy, r.oyz);
+  p[3 * k] = make_float4(r.om, r.a.b, r.a.y, 0.0f);
+}
+MRT_HD TRay tray_unstash(const TravIn& in) {
+  const float4* p = in.stash;
+  const uint32_t k = in.stash_stride;
+  const float4 a = p[0], b = p[k], c = p[2 * k], e = p[3 * k];
+  TRay r;
+  r.o = V3{a.x, a.y, a.z};
+  r.d = V3{a.w, b.x, b.y};
+  r.yx = b.z, r.yy = b.w, r.yz = c.x;
+  r.oyx = c.y, r.oyy = c.z, r.oyz = c.w;
+  r.om = e.x;
+  r.a.b = e.y, r.a.y = e.z;
+  return r;
+}
+
+// Inside a BLAS, `ret` is the world record after the instance/model record
+// that entered it, with kRetInstance set for an instance; the container of a
+// hit is recovered from that record when the ray finishes (trav_hit).
+constexpr uint32_t kNoRet = 0xFFFFFFFFu;
+constexpr uint32_t kRetInstance = 0x80000000u;
+constexpr uint32_t kExactMode = 0xFFFFu;  // Trav::sp of the reference's walk
+
+struct Trav {
+  TRay r;  // ray of the space being traversed (world, or instance object space)
+  uint32_t ray;  // pool index of the ray
+  uint32_t i, ret;
+  float best;
+  uint32_t prim, hit_ret;  // closest hit so far: primitive (kRefNone: none) and `ret` when found
+  uint4 s0, s1;  // current record (prefetched when i moves)
+  PathRng rng;   // the ray's stream, for scenes whose traversal draws (RNG variants only)
+  uint32_t sp;   // near-first walk: stack entries in use (kExactMode: the reference's walk)
+  float t2;      // near-first walk: the smallest t of the other hits it met (nf_finish)
+  NfLine nfl;    // near-first walk: the current space's rounding margin, for t <= cull(best) (nf_bound.h nf_line)
+  float nl;      // near-first walk: the current node's hits have t <= nl (its box's exit; +inf: unknown)
+  bool done;
+#ifdef MRT_DEBUG_BOUNDS
+  uint32_t steps;
+#endif
+};
+
+// LDS treelet (layout.h): records with kLdsTag in their index live in the
+// workgroup's LDS copy (mrt_lds), the rest in the global stream. Kernels
+// built with LDS=false never see a tagged index, nor does the host (which
+// has no LDS: the tagged branch exists on the device only).
+extern __shared__ uint4 mrt_lds[];
+template <bool LDS>
+MRT_HD void rec_load2(const TravIn& in, uint32_t i, uint4& a, uint4& b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (LDS && (i & kLdsTag)) {
+    const uint32_t j = i & kIdxMask;
+    a = mrt_lds[MRT_IDX(in.S, j, in.S.n_tlet, 22)];
+    b = mrt_lds[MRT_IDX(in.S, j + 1, in.S.n_tlet, 22)];
+  } else
+#endif
+  {
+    (void)MRT_IDX(in.S, i + 1, in.S.n_slots, 6);
+    const uint4* p = in.slots + MRT_IDX(in.S, i, in.S.n_slots, 5);  // one address, offset:16 for slot 2
+    a = p[0];
+    b = p[1];
+  }
+}
+template <bool LDS>
+MRT_HD uint4 rec_load1(const TravIn& in, uint32_t i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (LDS && (i & kLdsTag)) return mrt_lds[MRT_IDX(in.S, i & kIdxMask, in.S.n_tlet, 22)];
+#endif
+  return in.slots[MRT_IDX(in.S, i, in.S.n_slots, 7)];
+}
+
+template <bool LDS = false>
+MRT_HD Hit trav_hit(const TravIn& in, const Trav& t) {
+  uint32_t container = kRefNone;
+  if (t.hit_ret != kNoRet) {
+    const uint32_t rec = (t.hit_ret & ~kRetInstance) - 2;  // the instance/model record
+    container = make_ref((t.hit_ret & kRetInstance) ? MRT_REF_INSTANCE : MRT_REF_MODEL, rec_load1<LDS>(in, rec).x);
+  }
+  return Hit{t.best, t.prim, container};
+}
+
+MRT_HD TRay world_ray(const TravIn& in, uint32_t ray) {
+  const float4 o4 = in.ro[ray], d4 = in.rd[ray];
+  return make_tray(V3{o4.x, o4.y, o4.z}, V3{d4.x, d4.y, d4.z}, in.S.fast_ok);
+}
+
+// Load record t.i. Every region ends in an END record (handled by
+// trav_prim: leave the BLAS, or finish), so there is no bounds compare here.
+template <bool LDS = false>
+MRT_HD void trav_fetch(const TravIn& in, Trav& t) {
+#ifdef MRT_DEBUG_BOUNDS
+  if (++t.steps > (1u << 24)) {  // record and stop instead of looping
+    MRT_IDX(in.S, 0xFFFFFFF0u, 0u, 5);
+    t.done = true;
+    t.s1.w = KIND_END;  // a done lane never holds a box record (k_trace's box run)
+    return;
+  }
+#endif
+  rec_load2<LDS>(in, t.i, t.s0, t.s1);
+}
+
+// The region ended: leave the BLAS back to the world ray (geom.rs:405-409;
+// a model shares the world ray, an instance's object-space ray is replaced),
+// or finish the ray.
+MRT_HD void trav_end_index(const TravIn& in, Trav& t) {
+  if (t.ret == kNoRet) {
+    t.done = true;
+    return;
+  }
+  if (t.ret & kRetInstance) t.r = in.stash ? tray_unstash(in) : world_ray(in, t.ray);
+  t.i = t.ret & ~kRetInstance;
+  t.ret = kNoRet;
+}
+
+// ---- the near-first walk's start (walk_nf.h has the walk) -------------------
+// its culling bound: best * (1 + 2^-10)
+MRT_HD float nf_cull(float best) { return fmaf(fabsf(best), 0x1p-10f, best); }
+// t.nfc: the rounding margin's coefficients (nf_bound.h) of the space being
+// walked — set when the walk enters a space; nf_rho_at turns them into how
+// far a node's boxes are thickened (trav_box_index_nf)
+MRT_HD void nf_margin(const TravIn& in, Trav& t) {
+  const bool obj = t.ret != kNoRet && (t.ret & kRetInstance);
+  const NfBound& B = in.S.nfb;
+  const NfCoef c = obj ? nf_coef_object(B, t.r.o, t.r.a.b) : nf_coef_world(B, t.r.o, t.r.a.b);
+  t.nfl = nf_line(B, c, nf_cull(t.best), obj ? B.ao0 : B.aw0, obj ? B.ao1 : B.aw1, t.r.a.b, t.r.d);
+}
+// the walk starts at the NF world tree (trav_init): rays its bound does not
+// cover take the reference's walk instead
+MRT_HD void nf_start(const TravIn& in, Trav& t) {
+  if (nf_ray_ok(in.S.nfb, t.r.a.b)) {
+    nf_margin(in, t);
+    t.nl = INFINITY;
+  } else {
+    t.i = in.world_begin;
+    t.sp = kExactMode;
+  }
+}
+
+// Start ray `ray` of the pool (World::intersect(ray, in.tmin, tmax)).
+template <bool RNG = false, bool LDS = false>
+MRT_HD void trav_init(const TravIn& in, Trav& t, uint32_t ray, float tmax, uint32_t start = 0xFFFFFFFFu) {
+  if (RNG) {
+    const uint4 q = in.rng[ray];
+    t.rng = PathRng{(unsigned long long)q.x | ((unsigned long long)q.y << 32),
+                    (unsigned long long)q.z | ((unsigned long long)q.w << 32)};
+  }
+  t.r = world_ray(in, ray);
+  t.ray = ray;
+  t.i = start == 0xFFFFFFFFu ? in.world_begin : start;  // the near-first walk starts at its own world tree
+  t.sp = start == 0xFFFFFFFFu ? kExactMode : 0u;
+  t.t2 = INFINITY;
+  t.ret = kNoRet;
+  t.best = tmax;
+  t.prim = kRefNone;
+  t.hit_ret = kNoRet;
+  t.done = false;
+#ifdef MRT_DEBUG_BOUNDS
+  t.steps = 0;
+#endif
+  if (start != 0xFFFFFFFFu) nf_start(in, t);
+  trav_fetch<LDS>(in, t);
+}
+
+MRT_HD bool trav_at_box(const Trav& t) { return (int32_t)t.s1.w < 0; }  // kBoxFlag (layout.h)
+
+// The current record is a box: test it and move to the next record's index
+// (k_trace's box run loads at the top of each step); trav_box also loads it.
+template <bool COUNT>
+MRT_HD void trav_box_index(const TravIn& in, Trav& t, LocalCounters& lc) {
+  if (COUNT) lc.node_visits++;
+  V3 mn{u2f(t.s0.x), u2f(t.s0.y), u2f(t.s0.z)}, mx{u2f(t.s0.w), u2f(t.s1.x), u2f(t.s1.y)};
+  t.i = box_hit_any<COUNT>(mn, mx, t.r, in.tmin, t.best, &lc) ? (t.s1.w & ~kBoxFlag) : t.s1.z;
+}
+template <bool COUNT, bool LDS = false>
+MRT_HD void trav_box(const TravIn& in, Trav& t, LocalCounters& lc) {
+  trav_box_index<COUNT>(in, t, lc);
+  trav_fetch<LDS>(in, t);
+}
+
+// The ray's RNG state back to the pool (RNG variants, when the ray is done).
+MRT_HD void trav_store_rng(const TravIn& in, const Trav& t) {
+  in.rng[t.ray] = make_uint4((uint32_t)t.rng.s0, (uint32_t)(t.rng.s0 >> 32), (uint32_t)t.rng.s1,
+                             (uint32_t)(t.rng.s1 >> 32));
+}
+
+// Volume::intersect with a sphere target (geom.rs:609-653): entry and exit of
+// the target over the whole line, clipped to [tmin, best], then a distance
+// f.ln() * -1/density drawn from the ray's stream; the ln is looked up
+// (S.ln_table, upload.h) for the exact value of the host libm.
+MRT_HD bool volume_hit(const DevScene& S, const TravIn& in, Trav& t, uint4 s0, uint32_t vid, float& th) {
+  const V3 c{u2f(s0.x), u2f(s0.y), u2f(s0.z)};
+  const float rad = u2f(s0.w);
+  float te, tx;
+  if (!sphere_hit(c, rad, t.r.o, t.r.d, t.r.a, -INFINITY, INFINITY, te)) return false;
+  if (!sphere_hit(c, rad, t.r.o, t.r.d, t.r.a, te + 0.0001f, INFINITY, tx)) return false;
+  if (te < in.tmin) te = in.tmin;
+  if (tx > t.best) tx = t.best;
+  if (te >= tx) return false;
+  if (te < 0.0f) te = 0.0f;
+  const float len = sqrtf(length_squared(t.r.d));
+  const float inside = (tx - te) * len;
+  const uint32_t m = (uint32_t)(t.rng.next() >> 32) >> 9;  // the draw of f32() (mrt_rng.h)
+  const float dist = S.ln_table[MRT_IDX(S, m, 1u << 23, 14)] * S.vol_nid[MRT_IDX(S, vid, S.n_vol, 15)];
+  if (dist > inside) return false;
+  th = te + dist / len;
+  return true;
+}
+
+// The current record is a primitive, an instance or a model.
+// ALPHA: 0 no alpha tests (the specialisation for scenes without alpha-tested
+// triangles: the alpha test's registers would otherwise cost occupancy
+// everywhere), 1 alpha tests, 2 alpha tests over EXT surfaces.
+// trav_prim_index moves to the next record (or finishes the ray) without
+// loading it; trav_prim also loads it.
+template <bool COUNT, uint32_t ALPHA, bool RNG = false, bool LDS = false>
+MRT_HD void trav_prim_index(const TravIn& in, Trav& t, LocalCounters& lc) {
+  const DevScene& S = in.S;
+  const uint4 s0 = t.s0, s1 = t.s1;
+  const uint32_t kind = s1.w;
+  if (kind == KIND_END) {
+    trav_end_index(in, t);
+    return;
+  }
+  if (kind == KIND_TRI) {
+    if (COUNT) lc.triangle_tests++;
+    const uint4 s2 = rec_load1<LDS>(in, t.i + 2);
+    V3 a{u2f(s0.x), u2f(s0.y), u2f(s0.z)}, ab{u2f(s0.w), u2f(s1.x), u2f(s1.y)}, ac{u2f(s2.x), u2f(s2.y), u2f(s2.z)};
+    float th;
+    if (tri_hit(a, ab, ac, t.r.o, t.r.d, in.tmin, t.best, th)) {
+      const uint32_t id = s1.z & kTriIdMask;
+      if (!ALPHA || !(s1.z & kTriAlpha) || tri_alpha_pass<RNG, ALPHA == 2>(S, id, t.r.o, t.r.d, th, t.rng, lc)) {
+        t.best = th;
+        t.prim = make_ref(MRT_REF_TRIANGLE, id);
+        t.hit_ret = t.ret;
+      }
+    }
+    t.i = s2.w;
+  } else if (kind == KIND_SPHERE) {
+    if (COUNT) lc.sphere_tests++;
+    float th;
+    if (sphere_hit(V3{u2f(s0.x), u2f(s0.y), u2f(s0.z)}, u2f(s0.w), t.r.o, t.r.d, t.r.a, in.tmin, t.best, th)) {
+      t.best = th;
+      t.prim = make_ref(MRT_REF_SPHERE, s1.x);
+      t.hit_ret = t.ret;
+    }
+    t.i = s1.y;
+  } else if (RNG && kind == KIND_VOLUME) {
+    float th;
+    if (volume_hit(S, in, t, s0, s1.x, th)) {
+      t.best = th;
+      t.prim = make_ref(MRT_REF_VOLUME, s1.x);
+      t.hit_ret = t.ret;
+    }
+    t.i = s1.y;
+  } else if (kind == KIND_INST) {
+    if (COUNT) lc.instance_entries++;
+    V3 c0, c1, c2, c3;
+    load_m12(S.inst_inv + (size_t)MRT_IDX(S, s0.x, S.n_inst, 8) * 12, c0, c1, c2, c3);
+    // entered from the world region: t.r is the world ray here
+    if (in.stash) tray_stash(in, t.r);
+    t.r = make_tray(xform(c0, c1, c2, c3, t.r.o, 1.0f), xform(c0, c1, c2, c3, t.r.d, 0.0f), S.fast_ok);
+    t.ret = (t.i + 2) | kRetInstance;
+    t.i = s0.y;
+  } else {  // KIND_MODEL
+    if (COUNT) lc.model_entries++;
+    t.ret = t.i + 2;
+    t.i = s0.y;
+  }
+}
+template <bool COUNT, uint32_t ALPHA, bool RNG = false, bool LDS = false>
+MRT_HD void trav_prim(const TravIn& in, Trav& t, LocalCounters& lc) {
+  trav_prim_index<COUNT, ALPHA, RNG, LDS>(in, t, lc);
+  if (!t.done) trav_fetch<LDS>(in, t);
+}
+
+// Whole traversal of pool ray `ray` (one ray per thread); RNG: the
+// traversal's draws come from (and advance) `rng`.
+template <bool COUNT, bool RNG = false, bool EXT = false>
+MRT_HD Hit closest_hit(const TravIn& in, uint32_t ray, float tmax, LocalCounters& lc, PathRng& rng) {
+  Trav t;
+  trav_init(in, t, ray, tmax);
+  if (RNG) t.rng = rng;
+  while (!t.done) {
+    if (trav_at_box(t))
+      trav_box<COUNT>(in, t, lc);
+    else
+      trav_prim<COUNT, EXT ? 2u : 1u, RNG>(in, t, lc);
+  }
+  if (RNG) rng = t.rng;
+  return trav_hit(in, t);
+}
+
+}  // namespace mrt

@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define MRT_HD __host__ __device__ __forceinline__
 #else
 #define MRT_HD inline

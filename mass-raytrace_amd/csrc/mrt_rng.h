@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define MRT_RNG_HD __host__ __device__ __forceinline__
 #else
 #define MRT_RNG_HD inline

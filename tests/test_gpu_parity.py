@@ -12,6 +12,7 @@ import pytest
 import massrt
 import oracle
 from conftest import walk_keys
+from ray_gen import camera_rays, random_rays
 
 pytestmark = pytest.mark.gpu
 ASPECT = float(massrt.ASPECT_RATIO)
@@ -22,25 +23,6 @@ MESH = ["mesh_ply", "mesh_obj", "mesh_obj_textured"]
 
 def rel_l2(a, b):
     return float(np.linalg.norm(a.astype(np.float64) - b) / max(np.linalg.norm(b.astype(np.float64)), 1e-30))
-
-
-def random_rays(n, seed, span=15.0):
-    rng = np.random.default_rng(seed)
-    o = rng.uniform(-span, span, (n, 3)).astype(np.float32)
-    o[:, 1] = np.abs(o[:, 1]) + 0.5
-    d = rng.normal(size=(n, 3)).astype(np.float32)
-    return np.concatenate([o, d], 1)
-
-
-def camera_rays(cam, n, seed):
-    """Primary rays in the camera frustum (Camera::ray with jitter, world.rs:53-63)."""
-    rng = np.random.default_rng(seed)
-    f = cam.fields()
-    org, llc, hor, ver = f[0:3], f[3:6], f[6:9], f[9:12]
-    s = rng.random(n, dtype=np.float32)[:, None]
-    t = rng.random(n, dtype=np.float32)[:, None]
-    d = (((llc + hor * s) + ver * t) - org).astype(np.float32)
-    return np.concatenate([np.broadcast_to(org, (n, 3)), d], 1).astype(np.float32)
 
 
 @pytest.fixture(scope="module")

@@ -3,22 +3,30 @@ no GPU: the same rays through the preorder stream (build_host_scene(..., sibling
 through the default layout (BLAS regions with siblings together, every
 successor explicit) find the same closest hits, t bits included, after the
 same number of box tests; the early slab decision stays exact
-(tools/slab_check.cpp, which restates k_trace's walk on the host)."""
+(tools/slab_check.cpp, which runs k_trace's own walk code, compiled for the
+host, one ray at a time); and both walks' closest hits equal the oracle's."""
+import os
 import shutil
 import subprocess
 
+import numpy as np
 import pytest
 
+import massrt
+import oracle
 from conftest import GOLDEN, REPO
+from ray_gen import camera_rays, random_rays
 
 
 @pytest.fixture(scope="module")
 def slab_check(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("g++ missing")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")  # as the Makefile finds it
+    if not shutil.which(hipcc):
+        pytest.skip("hipcc missing")
     exe = tmp_path_factory.mktemp("slab") / "slab_check"
     lib = REPO / "mass-raytrace_amd" / "massrt"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", str(exe), str(REPO / "tools" / "slab_check.cpp"),
+    subprocess.run([hipcc, "--offload-host-only", "-x", "hip", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
+                    "-o", str(exe), str(REPO / "tools" / "slab_check.cpp"),
                     f"-L{lib}", "-lmassrt", f"-Wl,-rpath,{lib}"], check=True)
     return exe
 
@@ -49,8 +57,8 @@ def _bound(stdout: str):
 
 @pytest.mark.parametrize("scene", ["cornell", "sphere_grid", "cube_field"])
 def test_near_first_walk_finds_the_reference_hits(slab_check, scene):
-    """The verified near-first walk (nf_tree.cpp's trees, path.h's steps,
-    restated by tools/slab_check.cpp walk_nf): on camera and bounce rays the
+    """The verified near-first walk (nf_tree.cpp's trees, walk_nf.h's steps,
+    which tools/slab_check.cpp walk_nf runs on the host): on camera and bounce rays the
     same closest hits as the reference's left-first walk — primitive,
     container, t bits — with fewer record loads; the stack stays within
     kNfStack. Every hit the reference's tests accept lies within the walk's
@@ -100,7 +108,7 @@ def _wild_checked(stdout: str, n_wild: int):
 
 def test_wild_instance_cornell(slab_check):
     """Cornell's thin light (cond |F||G| ~ 1.4e4: a wild instance, nf_tree.cpp wild()): its hits lie within its
-    own instance term of its world box, which the walk tests at the wild leaf (path.h nf_wild_enter) instead of
+    own instance term of its world box, which the walk tests at the wild leaf (walk_nf.h nf_wild_enter) instead of
     entering it on every ray; the closest hits stay the reference's."""
     r = subprocess.run([str(slab_check), "cornell", "30000", str(GOLDEN), "nf"], capture_output=True, text=True,
                        timeout=300)
@@ -153,3 +161,42 @@ def test_near_first_tangent_rays(slab_check, scene):
     assert " nf: 0 of 100000 rays differ" in line, line
     checks, worst, over, bline = _bound(r.stdout)
     assert checks > 100000 and over == 0 and worst < 0.25, bline
+
+
+# ---- the walks' closest hits against the oracle, on the host ---------------------
+# tests/test_gpu_parity.py's test_golden_rays_bit_exact and test_trace_rays_bit_exact
+# without a GPU, on the code the GPU runs: slab_check's `hits` / `hits-nf` modes are
+# k_rays_in -> the reference's / the near-first walk -> k_rays_out, one ray at a time.
+SMALL = ["cornell", "sphere_grid", "cube_field"]
+WALKS = ["hits", "hits-nf"]
+
+
+def _host_hits(slab_check, scene, walk, rays, tmp_path):
+    rays_file, out_file = tmp_path / "rays.f32", tmp_path / f"{walk}.u32"
+    np.ascontiguousarray(rays, dtype=np.float32).tofile(rays_file)
+    r = subprocess.run([str(slab_check), scene, "0", str(GOLDEN), walk, str(rays_file), str(out_file)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return np.fromfile(out_file, dtype=np.uint32).reshape(-1, 4)
+
+
+@pytest.mark.parametrize("scene", SMALL)
+def test_host_walks_golden_rays_bit_exact(slab_check, scene, tmp_path):
+    g = np.load(GOLDEN / "oracle_golden.npz")
+    for walk in WALKS:
+        hits = _host_hits(slab_check, scene, walk, g["rays"], tmp_path)
+        assert np.array_equal(hits, g[f"{scene}_hits"]), f"{walk}: {int((hits != g[f'{scene}_hits']).any(1).sum())} rays differ"
+
+
+@pytest.mark.parametrize("scene", SMALL)
+def test_host_walks_equal_the_oracle(slab_check, scene, tmp_path):
+    """20,000 random and 20,000 camera rays: primitive, container, t bits and
+    front face of both walks equal oracle.Scene.trace_rays."""
+    aspect = float(massrt.ASPECT_RATIO)
+    _, cam = massrt.Builder(1).builtin(scene, aspect, GOLDEN).desc()
+    rays = np.concatenate([random_rays(20_000, 1), camera_rays(cam, 20_000, 2)])
+    want = oracle.Scene(1).builtin(scene, aspect, GOLDEN).trace_rays(rays)
+    assert int((want[:, 0] != 0).sum()) > 5_000  # the sample hits something
+    for walk in WALKS:
+        hits = _host_hits(slab_check, scene, walk, rays, tmp_path)
+        assert np.array_equal(hits, want), f"{walk}: {int((hits != want).any(1).sum())} rays differ"

@@ -1,12 +1,25 @@
-// slab_check — host-side restatement of k_trace's early slab decision
-// (path.h make_tray / slab_fast / box_hit_any), run over the record stream of
-// a built-in scene on camera rays and one-bounce rays, no GPU needed: every
-// box the early decision settles must get the exact BoundingBox::hit answer
-// (IEEE quotients, geom.rs:218-247), and the fraction left to the exact test
-// is reported. Round 2 used it to find that mesh_ply's vertices at ~1e-16
-// (sin(pi)) had switched the whole scene to the exact test.
-//   g++ -O2 -std=c++17 -ffp-contract=off -o tools/slab_check tools/slab_check.cpp -Lmass-raytrace_amd/massrt
-//       -lmassrt -Wl,-rpath,$PWD/mass-raytrace_amd/massrt && tools/slab_check mesh_ply 20000 assets
+// slab_check — k_trace's two walks run on the host, no GPU needed: a driver of
+// the device headers' own step functions (walk.h trav_*, walk_nf.h trav_*_nf /
+// nf_finish, compiled here for the host: the same source, the same bits) over
+// the record stream of a built-in scene, on camera rays, one-bounce rays and
+// stress rays. What is written here is only the evidence that must stay
+// independent of that code:
+//   * box_exact, BoundingBox::hit with IEEE quotients (geom.rs:218-247): every
+//     box the early slab decision settles, and every answer of the exact test
+//     (box_hit_exact, the qfast path), must equal it; the fraction left to the
+//     exact test is reported. Round 2 used it to find that mesh_ply's vertices
+//     at ~1e-16 (sin(pi)) had switched the whole scene to the exact test.
+//   * the double-precision bound checks (check_hit, check_hit_wild,
+//     cone_rho_min): every hit the reference's tests accept lies within the
+//     near-first walk's rounding margin of its boxes (nf_bound.h).
+//   * the comparison of the two walks' closest hits, the sibling layout
+//     against the plain preorder stream, and the walk statistics.
+//   hipcc --offload-host-only -x hip -O2 -std=c++17 -ffp-contract=off -fno-fast-math -o tools/slab_check
+//       tools/slab_check.cpp -Lmass-raytrace_amd/massrt -lmassrt -Wl,-rpath,$PWD/mass-raytrace_amd/massrt
+//   (plain g++ -O2 -std=c++17 -ffp-contract=off builds it too, to the same output: devbase.h's fallback types)
+//   tools/slab_check mesh_ply 20000 assets [layout | nf | graze | tangent]
+//   tools/slab_check cornell 0 tests/golden hits|hits-nf rays.f32 out.u32
+//       n x 6 float32 rays in, n x 4 uint32 out in mrt_trace_rays' layout (k_rays_in -> walk -> k_rays_out)
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -18,59 +31,26 @@
 #include <unordered_map>
 #include <vector>
 
+#include "../mass-raytrace_amd/csrc/device/material.h"
 #include "../mass-raytrace_amd/csrc/device/upload.h"
+#include "../mass-raytrace_amd/csrc/device/walk_nf.h"
 
 using namespace mrt;
 
 namespace {
 
-float f(uint32_t u) {
-  float x;
-  memcpy(&x, &u, 4);
-  return x;
-}
-struct V {
-  float x, y, z;
-};
-V sub(V a, V b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-float dot(V a, V b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-V cross(V a, V b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+using V = V3;
+const float kTmin = 0.001f;
 
-struct Ray {
-  V o, d;
-  float y[3], oy[3], om;
-  bool fast;
-};
-bool dir_ok(float c) {
-  float a = fabsf(c);
-  return a >= 0x1p-20f && a <= 0x1p20f;
-}
-Ray make_ray(V o, V d, bool scene_fast) {
-  Ray r{o, d, {}, {}, 0, false};
-  const float oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
-  float m = 0;
-  for (int k = 0; k < 3; ++k) {
-    r.y[k] = 1.0f / dd[k];
-    r.oy[k] = oo[k] * r.y[k];
-    m = std::max(m, fabsf(r.oy[k]));
-  }
-  r.om = std::max(m * 0x1p-20f, 0x1p-120f);
-  // early-decision domain (path.h make_tray): finite origin within 2^28, |d| in [2^-20, 2^20]
-  auto o_ok = [](float c) { return fabsf(c) <= 0x1p28f; };
-  r.fast = scene_fast && o_ok(o.x) && o_ok(o.y) && o_ok(o.z) && dir_ok(d.x) && dir_ok(d.y) && dir_ok(d.z);
-  return r;
-}
 // BoundingBox::hit with IEEE quotients (fminf/fmaxf = minNum/maxNum, as v_min/v_max)
-bool box_exact(const float mn[3], const float mx[3], const Ray& r, float tmin, float tmax) {
-  const float oo[3] = {r.o.x, r.o.y, r.o.z}, dd[3] = {r.d.x, r.d.y, r.d.z};
-  float t0 = tmin, t1 = tmax;
+bool box_exact(V mn, V mx, V o, V d, float tmin, float tmax) {
+  const float lo[3] = {mn.x, mn.y, mn.z}, hi[3] = {mx.x, mx.y, mx.z}, oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
   float a[3], b[3];
-  for (int k = 0; k < 3; ++k) a[k] = (mn[k] - oo[k]) / dd[k], b[k] = (mx[k] - oo[k]) / dd[k];
-  t0 = fmaxf(fmaxf(fminf(a[0], b[0]), fminf(a[1], b[1])), fmaxf(fminf(a[2], b[2]), tmin));
-  t1 = fminf(fminf(fmaxf(a[0], b[0]), fmaxf(a[1], b[1])), fminf(fmaxf(a[2], b[2]), tmax));
+  for (int k = 0; k < 3; ++k) a[k] = (lo[k] - oo[k]) / dd[k], b[k] = (hi[k] - oo[k]) / dd[k];
+  const float t0 = fmaxf(fmaxf(fminf(a[0], b[0]), fminf(a[1], b[1])), fmaxf(fminf(a[2], b[2]), tmin));
+  const float t1 = fminf(fminf(fmaxf(a[0], b[0]), fmaxf(a[1], b[1])), fminf(fmaxf(a[2], b[2]), tmax));
   return !(t1 < t0);
 }
-float margin(const Ray& r, float t0, float t1) { return std::fma(fabsf(t0) + fabsf(t1), 0x1p-19f, r.om); }
 
 struct Stats {
   uint64_t boxes = 0, undecided = 0, wrong = 0;
@@ -79,55 +59,6 @@ struct Stats {
   uint64_t wild_skips = 0;  // wild instances passed by on their own box test
   uint64_t prims = 0;       // primitive tests
 };
-// path.h box_hit_any's early decision: 1 hit, 0 miss, -1 left to the exact test
-int early_decide(const float mn[3], const float mx[3], const Ray& r, float tmin, float best) {
-  if (!r.fast) return -1;
-  float a[3], b[3];
-  for (int k = 0; k < 3; ++k) a[k] = std::fma(mn[k], r.y[k], -r.oy[k]), b[k] = std::fma(mx[k], r.y[k], -r.oy[k]);
-  const float t0 = fmaxf(fmaxf(fminf(a[0], b[0]), fminf(a[1], b[1])), fmaxf(fminf(a[2], b[2]), tmin));
-  const float t1 = fminf(fminf(fmaxf(a[0], b[0]), fmaxf(a[1], b[1])), fminf(fmaxf(a[2], b[2]), best));
-  const float m = margin(r, t0, t1), gap = t1 - t0;
-  return gap > m ? 1 : (-gap > m ? 0 : -1);
-}
-
-bool sphere_hit(V c, float rad, V o, V d, float tmin, float tmax, float& t) {
-  V oc = sub(o, c);
-  float a = dot(d, d), hb = dot(oc, d), cc = dot(oc, oc) - rad * rad, disc = hb * hb - a * cc;
-  if (disc < 0.0f) return false;
-  float sq = sqrtf(disc), root = (-hb - sq) / a;
-  if (root < tmin || tmax < root) {
-    root = (-hb + sq) / a;
-    if (root < tmin || tmax < root) return false;
-  }
-  t = root;
-  return true;
-}
-bool tri_hit(V a, V ab, V ac, V o, V d, float tmin, float tmax, float& t) {
-  V p = cross(d, ac);
-  float det = dot(ab, p);
-  if (fabsf(det) < 0.000001f) return false;
-  float inv = 1.0f / det;
-  V tv = sub(o, a);
-  float u = dot(tv, p) * inv;
-  if (u < 0.0f || u > 1.0f) return false;
-  V qv = cross(tv, ab);
-  float v = dot(d, qv) * inv;
-  if (v < 0.0f || v + u > 1.0f) return false;
-  float tt = dot(ac, qv) * inv;
-  if (tt < tmin || tt > tmax) return false;
-  t = tt;
-  return true;
-}
-V xf(const float* m, V p, float w) {  // c0.xyz c1.xyz c2.xyz c3.xyz
-  return {((m[0] * p.x + m[3] * p.y) + m[6] * p.z) + m[9] * w, ((m[1] * p.x + m[4] * p.y) + m[7] * p.z) + m[10] * w,
-          ((m[2] * p.x + m[5] * p.y) + m[8] * p.z) + m[11] * w};
-}
-
-struct Result {
-  uint32_t prim, container;
-  float t;
-};
-const float kTmin = 0.001f;
 
 // `bound` checks (nf_bound.h): every primitive test of the
 // reference walk is repeated with t_max = inf; an accepted hit X = o + t d
@@ -197,19 +128,18 @@ void map_nf_tree(const HostScene& s, uint32_t root, std::vector<uint8_t>& seen_b
   }
 }
 // the smallest rho over the NF nodes a hit's primitive (vnf slot) sits below,
-// each with its normal cone (path.h trav_box_index_nf), at the hit's t
+// each with its normal cone (walk_nf.h trav_box_index_nf), at the hit's t
 float cone_rho_min(const HostScene& s, uint32_t vslot, V o, V d, float t, bool obj) {
-  const mrt::V3 oo{o.x, o.y, o.z}, dd{d.x, d.y, d.z};
   const float d2 = (d.x * d.x + d.y * d.y) + d.z * d.z;
   const NfBound& B = s.nfb;
-  const NfCoef c = obj ? nf_coef_object(B, oo, d2) : nf_coef_world(B, oo, d2);
-  const NfLine l = nf_line(B, c, t, obj ? B.ao0 : B.aw0, obj ? B.ao1 : B.aw1, d2, dd);
+  const NfCoef c = obj ? nf_coef_object(B, o, d2) : nf_coef_world(B, o, d2);
+  const NfLine l = nf_line(B, c, t, obj ? B.ao0 : B.aw0, obj ? B.ao1 : B.aw1, d2, d);
   float rho = nf_rho_at(B, c, t);
   if (!(B.kc > 0) || vslot >= g_leaf_parent.size()) return rho;
   const uint32_t* w = s.slots.data();
   for (uint32_t n = g_leaf_parent[vslot]; n != ~0u; n = g_nf_parent[n]) {
     const uint32_t* a = w + 4 * (size_t)n;
-    rho = std::min(rho, nf_rho_cone(l, t, a[0], a[1], a[2], a[3], dd));
+    rho = std::min(rho, nf_rho_cone(l, t, a[0], a[1], a[2], a[3], d));
   }
   return rho;
 }
@@ -222,8 +152,7 @@ double box_dist(const float* b, double x, double y, double z) {
 void check_hit(const HostScene& s, const float* box, V o, V d, float t, bool obj, uint32_t vslot = ~0u) {
   if (!box || std::isnan(box[0])) return;
   const double x = (double)o.x + (double)t * d.x, y = (double)o.y + (double)t * d.y, z = (double)o.z + (double)t * d.z;
-  const mrt::V3 oo{o.x, o.y, o.z};
-  const NfCoef c = obj ? nf_coef_object(s.nfb, oo, dot(d, d)) : nf_coef_world(s.nfb, oo, dot(d, d));
+  const NfCoef c = obj ? nf_coef_object(s.nfb, o, dot(d, d)) : nf_coef_world(s.nfb, o, dot(d, d));
   // the rho of every NF node above the primitive, narrowed by its cone
   const float rho = vslot == ~0u ? nf_rho_at(s.nfb, c, t) : cone_rho_min(s, vslot, o, d, t, obj);
   const float cap = nf_rho_at(s.nfb, c, INFINITY);
@@ -248,8 +177,7 @@ void check_hit_wild(const HostScene& s, uint32_t inst, V o, V d, float t) {
   const NfWild e = wild_entry(s, it->second);
   const float box[6] = {e.mn[0], e.mn[1], e.mn[2], e.mx[0], e.mx[1], e.mx[2]};
   const double x = (double)o.x + (double)t * d.x, y = (double)o.y + (double)t * d.y, z = (double)o.z + (double)t * d.z;
-  const mrt::V3 oo{o.x, o.y, o.z};
-  const float rho = nf_rho_wild(e, oo, dot(d, d), t), cap = nf_rho_wild(e, oo, dot(d, d), INFINITY);
+  const float rho = nf_rho_wild(e, o, dot(d, d), t), cap = nf_rho_wild(e, o, dot(d, d), INFINITY);
   const double dist = box_dist(box, x, y, z);
   g_bc->checks++;
   g_bc->wild_checks++;
@@ -267,369 +195,211 @@ const float* leaf_box(const HostScene& s, uint32_t base, uint32_t id) {
   return &s.nf_leaf_box[6 * (size_t)(s.vnf_base[base] + id)];
 }
 
-// plain stream (layout.h): exact box tests
-Result walk_plain(const HostScene& s, V o, V d, Stats* st = nullptr) {
-  const uint32_t* w = s.slots.data();
-  Ray wr = make_ray(o, d, s.early_ok), r = wr;
-  uint32_t i = s.world_begin, ret = ~0u, hit_ret = ~0u;
-  float best = INFINITY;
-  uint32_t prim = 0;
-  for (;;) {
-    const uint32_t* a = w + 4 * (size_t)i;
-    const uint32_t k = a[7];
-    if (k & kBoxFlag) {
-      float mn[3] = {f(a[0]), f(a[1]), f(a[2])}, mx[3] = {f(a[3]), f(a[4]), f(a[5])};
-      const bool truth = box_exact(mn, mx, r, kTmin, best);
-      if (st) {
-        st->boxes++;
-        st->loads += 2;
-        const int dec = early_decide(mn, mx, r, kTmin, best);
-        if (dec < 0) st->undecided++;
-        else if ((dec != 0) != truth) st->wrong++;
-      }
-      i = truth ? (k & ~kBoxFlag) : a[6];
-    } else if (k == KIND_END) {
-      if (st) st->loads += 2;
-      if (ret == ~0u) break;
-      if (ret & 0x80000000u) r = wr;
-      i = ret & 0x7FFFFFFFu;
-      ret = ~0u;
-    } else if (k == KIND_SPHERE) {
-      float t;
-      if (st) st->loads += 2;
-      if (sphere_hit({f(a[0]), f(a[1]), f(a[2])}, f(a[3]), r.o, r.d, kTmin, best, t))
-        best = t, prim = MRT_REF(MRT_REF_SPHERE, a[4]), hit_ret = ret;
-      if (g_bc && sphere_hit({f(a[0]), f(a[1]), f(a[2])}, f(a[3]), r.o, r.d, kTmin, INFINITY, t))
-        check_hit(s, leaf_box(s, VNF_SPHERE, a[4]), r.o, r.d, t, false);  // spheres are world objects
-      i = a[5];  // next (layout.h)
-    } else if (k == KIND_TRI) {
-      float t;
-      if (st) st->loads += 3;
-      if (tri_hit({f(a[0]), f(a[1]), f(a[2])}, {f(a[3]), f(a[4]), f(a[5])}, {f(a[8]), f(a[9]), f(a[10])}, r.o, r.d,
-                  kTmin, best, t))
-        best = t, prim = MRT_REF(MRT_REF_TRIANGLE, a[6] & kTriIdMask), hit_ret = ret;
-      if (g_bc && tri_hit({f(a[0]), f(a[1]), f(a[2])}, {f(a[3]), f(a[4]), f(a[5])}, {f(a[8]), f(a[9]), f(a[10])}, r.o,
-                          r.d, kTmin, INFINITY, t)) {
-        const bool inst = ret != ~0u && (ret & 0x80000000u);
-        check_hit(s, leaf_box(s, VNF_TRI, a[6] & kTriIdMask), r.o, r.d, t, inst, s.vnf_base[VNF_TRI] + (a[6] & kTriIdMask));
-        if (inst) {  // the same hit in world space against the instance's world box
-          const uint32_t cid = w[4 * (size_t)((ret & 0x7FFFFFFFu) - 2)];
-          if (s.nf_inst_wild.empty() || !s.nf_inst_wild[cid])
-            check_hit(s, leaf_box(s, VNF_INST, cid), wr.o, wr.d, t, false);
-          else  // a wild instance: its world box within the wild margin (nf_bound.h nf_rho_wild)
-            check_hit_wild(s, cid, wr.o, wr.d, t);
-        } else if (ret != ~0u) {  // a model's triangle: its world box too
-          const uint32_t cid = w[4 * (size_t)(ret - 2)];
-          check_hit(s, leaf_box(s, VNF_MODEL, cid), wr.o, wr.d, t, false);
-        }
-      }
-      i = a[11];  // next (layout.h)
-    } else if (k == KIND_INST) {
-      const float* m = &s.inst_inv[12 * (size_t)a[0]];
-      if (st) st->loads += 5, st->entries++;
-      r = make_ray(xf(m, wr.o, 1.0f), xf(m, wr.d, 0.0f), s.early_ok);
-      ret = (i + 2) | 0x80000000u;
-      i = a[1];
-    } else if (k == KIND_MODEL) {
-      if (st) st->loads += 2;
-      ret = i + 2;
-      i = a[1];
-    } else {
-      fprintf(stderr, "plain: unsupported kind %u\n", k);
-      exit(2);
-    }
-  }
-  uint32_t cont = 0;
-  if (hit_ret != ~0u) {
-    const uint32_t rec = (hit_ret & 0x7FFFFFFFu) - 2;
-    cont = MRT_REF((hit_ret & 0x80000000u) ? MRT_REF_INSTANCE : MRT_REF_MODEL, w[4 * (size_t)rec]);
-  }
-  return {prim, cont, best};
-}
+// ---- the driver: one ray at a time through the device headers' steps ----------
+// A one-ray pool (k_rays_in's slot 0) and the walk's inputs over it.
+struct OneRay {
+  float4 ro, rd;
+  TravIn in;
+  OneRay(const DevScene& S, V o, V d)
+      : ro(make_float4(o.x, o.y, o.z, 0.0f)), rd(make_float4(d.x, d.y, d.z, 0.0f)),
+        in{S, reinterpret_cast<const uint4*>(S.slots), S.world_begin, &ro, &rd, kTmin} {}
+};
+struct Scene {
+  const HostScene& s;
+  DevScene S;
+  explicit Scene(const HostScene& hs) : s(hs), S(host_dev_scene(hs)) {}
+};
+V box_lo(const Trav& t) { return V{u2f(t.s0.x), u2f(t.s0.y), u2f(t.s0.z)}; }
+V box_hi(const Trav& t) { return V{u2f(t.s0.w), u2f(t.s1.x), u2f(t.s1.y)}; }
 
-// path.h nf_node_test: both children's boxes of an NF node (layout.h) at
-// once, from the planes' 8-bit steps. Fast rays: t = q * (2^e * y) +
-// (o * y - oy) per plane with the early decision's margin plus the node's
-// |o * y - oy| term — "miss" only when certain, anything else a hit
-// (conservative: the walk's hits are checked, its boxes never need to be
-// exact); other rays: the exact test on the decoded planes widened by an ulp.
-void node_test(const uint32_t* a, const Ray& r, float tmin, float tmax, float nfm, bool hit[2], float ent[2],
-               float ex[2]) {
-  const float o[3] = {f(a[0]), f(a[1]), f(a[2])};
-  uint8_t q[12];
-  for (int j = 0; j < 3; ++j)
-    for (int b = 0; b < 4; ++b) q[4 * j + b] = (uint8_t)(a[4 + j] >> (8 * b));
-  float sc[3], A[3], B[3], BL[3], BH[3], mb = 0.0f;
-  for (int k = 0; k < 3; ++k) {
-    sc[k] = f(((a[3] >> (8 * k)) & 0xFFu) << 23);
-    A[k] = sc[k] * r.y[k];
-    B[k] = std::fma(o[k], r.y[k], -r.oy[k]);
-    BL[k] = std::fma(-nfm, r.y[k], B[k]);
-    BH[k] = std::fma(nfm, r.y[k], B[k]);
-    mb = std::max(mb, std::max(fabsf(BL[k]), fabsf(BH[k])));
-  }
-  const float mabs = std::fma(mb, 0x1p-20f, r.om);
-  for (int c = 0; c < 2; ++c) {
-    const uint8_t* lo = q + 6 * c;
-    const uint8_t* hi = q + 6 * c + 3;
-    if (r.fast) {
-      float tl[3], th[3];
-      for (int k = 0; k < 3; ++k) tl[k] = std::fma((float)lo[k], A[k], BL[k]), th[k] = std::fma((float)hi[k], A[k], BH[k]);
-      const float t0 = fmaxf(fmaxf(fminf(tl[0], th[0]), fminf(tl[1], th[1])), fmaxf(fminf(tl[2], th[2]), tmin));
-      const float t1 = fminf(fminf(fmaxf(tl[0], th[0]), fmaxf(tl[1], th[1])), fminf(fmaxf(tl[2], th[2]), tmax));
-      const float m = std::fma(fabsf(t0) + fabsf(t1), 0x1p-19f, mabs);
-      const bool force = (a[7] & (kNfForceL << c)) != 0;
-      hit[c] = !(t0 - t1 > m) || force;
-      ent[c] = t0;
-      ex[c] = force ? INFINITY : std::fma(m, 2.0f, t1);  // a wild instance's hits: no exit bound
-    } else {
-      float mn[3], mx[3];
-      for (int k = 0; k < 3; ++k) {
-        const float pl = std::fma((float)lo[k], sc[k], o[k]) - nfm, ph = std::fma((float)hi[k], sc[k], o[k]) + nfm;
-        mn[k] = pl - std::fma(fabsf(pl), 0x1p-23f, 0x1p-140f);
-        mx[k] = ph + std::fma(fabsf(ph), 0x1p-23f, 0x1p-140f);
-      }
-      hit[c] = box_exact(mn, mx, r, tmin, tmax) || (a[7] & (kNfForceL << c));
-      ent[c] = 0.0f;
-      ex[c] = INFINITY;
-    }
+// Before a reference box step: the early slab decision (slab_fast /
+// slab_margin, where it decides) and the exact test (box_hit_exact: qfast in
+// its domain) against the IEEE-quotient truth.
+void check_box(const TravIn& in, const Trav& t, Stats& st) {
+  const V mn = box_lo(t), mx = box_hi(t);
+  const bool truth = box_exact(mn, mx, t.r.o, t.r.d, in.tmin, t.best);
+  float t0, t1;
+  slab_fast(mn, mx, t.r, in.tmin, t.best, t0, t1);
+  const float m = slab_margin(t.r, t0, t1), gap = t1 - t0;
+  if (gap > m) st.wrong += !truth;
+  else if (-gap > m) st.wrong += truth;
+  st.wrong += box_hit_exact(mn, mx, t.r, in.tmin, t.best) != truth;
+}
+// Before a reference primitive step: the bound checks of its record, the real
+// test repeated at t_max = inf ((wo, wd): the world ray)
+void check_prim(const HostScene& s, const TravIn& in, const Trav& t, V wo, V wd) {
+  const uint4 s0 = t.s0, s1 = t.s1;
+  float th;
+  if (s1.w == KIND_SPHERE) {  // spheres are world objects
+    if (sphere_hit(V{u2f(s0.x), u2f(s0.y), u2f(s0.z)}, u2f(s0.w), t.r.o, t.r.d, t.r.a, in.tmin, INFINITY, th))
+      check_hit(s, leaf_box(s, VNF_SPHERE, s1.x), t.r.o, t.r.d, th, false);
+  } else if (s1.w == KIND_TRI) {
+    const uint4 s2 = rec_load1<false>(in, t.i + 2);
+    const V a{u2f(s0.x), u2f(s0.y), u2f(s0.z)}, ab{u2f(s0.w), u2f(s1.x), u2f(s1.y)}, ac{u2f(s2.x), u2f(s2.y), u2f(s2.z)};
+    if (!tri_hit(a, ab, ac, t.r.o, t.r.d, in.tmin, INFINITY, th)) return;
+    const uint32_t id = s1.z & kTriIdMask;
+    const bool inst = t.ret != kNoRet && (t.ret & kRetInstance);
+    check_hit(s, leaf_box(s, VNF_TRI, id), t.r.o, t.r.d, th, inst, s.vnf_base[VNF_TRI] + id);
+    if (t.ret == kNoRet) return;
+    // the same hit in world space against the container's world box
+    const uint32_t cid = rec_load1<false>(in, (t.ret & ~kRetInstance) - 2).x;
+    if (!inst) check_hit(s, leaf_box(s, VNF_MODEL, cid), wo, wd, th, false);
+    else if (s.nf_inst_wild.empty() || !s.nf_inst_wild[cid]) check_hit(s, leaf_box(s, VNF_INST, cid), wo, wd, th, false);
+    else check_hit_wild(s, cid, wo, wd, th);  // its world box within the wild margin (nf_bound.h nf_rho_wild)
   }
 }
 
-// The verified near-first walk (layout.h; path.h trav_*_nf, nf_finish)
-// restated on the host: the NF trees near child first with a stack, the
-// reference's tie rule by order keys, the reachability check of the winner
-// on the reference stream, the reference's walk where it fails.
-uint64_t nf_key(const HostScene& s, uint32_t prim, uint32_t ret) {
-  const uint32_t* w = s.slots.data();
-  const uint32_t kind = prim >> 28, id = prim & 0x0FFFFFFFu;
-  auto entry = [&](uint32_t base, uint32_t i, int word) { return s.vnf_leaf[2 * (size_t)(s.vnf_base[base] + i) + word]; };
-  if (kind == MRT_REF_SPHERE) return (uint64_t)entry(VNF_SPHERE, id, 1) << 32;
-  const uint32_t k = entry(VNF_TRI, id, 1);
-  if (k & kWorldKey) return (uint64_t)(k & ~kWorldKey) << 32;
-  const uint32_t cid = w[4 * (size_t)((ret & 0x7FFFFFFFu) - 2)];
-  return ((uint64_t)entry((ret & 0x80000000u) ? VNF_INST : VNF_MODEL, cid, 1) << 32) | k;
-}
-Result walk_nf(const HostScene& s, V o, V d, Stats* st, uint64_t* fallbacks, uint64_t* starts_ref = nullptr) {
-  const uint32_t* w = s.slots.data();
-  const Ray wr = make_ray(o, d, s.early_ok);
-  if (!nf_ray_ok(s.nfb, dot(d, d))) {  // path.h nf_start: the bound does not cover this ray
-    if (starts_ref) ++*starts_ref;
-    return walk_plain(s, o, d, st);
+// One step of the reference walk and the fetch of the next record. st: the
+// record loads of the step by kind; check: the box and bound checks too.
+template <uint32_t ALPHA>
+void ref_step(const Scene& c, const TravIn& in, Trav& t, LocalCounters& lc, Stats* st, bool check, V wo, V wd) {
+  if (trav_at_box(t)) {
+    if (st) st->loads += 2;
+    if (st && check) check_box(in, t, *st);
+    trav_box_index<true>(in, t, lc);
+  } else {
+    const uint32_t kind = t.s1.w;
+    if (st) st->loads += kind == KIND_TRI ? 3 : kind == KIND_INST ? 5 : 2;  // END, sphere, model: 2
+    if (st && kind == KIND_INST) st->entries++;
+    if (check && g_bc) check_prim(c.s, in, t, wo, wd);
+    trav_prim_index<true, ALPHA>(in, t, lc);
   }
-  Ray r = wr;
-  uint32_t i = s.nf_world, ret = ~0u, hit_ret = ~0u, prim = 0;
-  float best = INFINITY, t2 = INFINITY, nl = INFINITY;
-  NfCoef nfc{};
-  NfLine nfl{};
-  std::vector<uint32_t> stack;
-  std::vector<float> stack_nl;
-  auto cull = [&]() { return std::fma(fabsf(best), 0x1p-10f, best); };
-  auto margin = [&]() {  // path.h nf_margin
-    const bool obj = ret != ~0u && (ret & 0x80000000u);
-    const mrt::V3 oo{r.o.x, r.o.y, r.o.z};
-    nfc = obj ? nf_coef_object(s.nfb, oo, dot(r.d, r.d)) : nf_coef_world(s.nfb, oo, dot(r.d, r.d));
-    nfl = nf_line(s.nfb, nfc, cull(), obj ? s.nfb.ao0 : s.nfb.aw0, obj ? s.nfb.ao1 : s.nfb.aw1, dot(r.d, r.d),
-                  mrt::V3{r.d.x, r.d.y, r.d.z});
-  };
-  margin();
-  auto pop = [&]() {
-    while (!stack.empty()) {
-      const uint32_t v = stack.back();
-      stack.pop_back();
-      nl = INFINITY;
-      stack_nl.pop_back();
-      if (v != 0x80000000u) {
-        i = v;
-        return true;
-      }
-      const bool inst = (ret & 0x80000000u) != 0;
-      ret = ~0u;
-      if (inst) {
-        r = wr;
-        if (st) st->loads += 2;
-        margin();
-      }
-    }
-    return false;
-  };
-  auto better = [&](float t, uint32_t pr) {
-    if (t < best) return true;
-    if (!(t == best)) return false;
-    if (prim == 0) return true;
-    return nf_key(s, pr, ret) > nf_key(s, prim, hit_ret);
-  };
-  auto hit = [&](float t, uint32_t pr) {
-    if (t <= best && better(t, pr)) {
-      t2 = fminf(t2, best);
-      best = t, prim = pr, hit_ret = ret;
-      nfl.rcb = nf_rho_node(nfl, cull());
-    } else {
-      t2 = fminf(t2, t);
-    }
-  };
-  for (;;) {
-    const uint32_t* a = w + 4 * (size_t)i;
-    const uint32_t k = a[7];
-    if (k & kBoxFlag) {  // a node: both children's boxes, the nearer hit child first
-      if (st) st->boxes += 2, st->loads += 2;
-      bool h[2];
-      float e[2], x[2];
-      const float tn = fminf(cull(), nl);
-      // the cone while this ray's worst-case generic term is worth it (path.h: while some lane's is)
-      const float rho = s.nfb.kc > 0 && nfl.rg * tn > s.nfb.kcmin
-                            ? nf_rho_cone(nfl, tn, a[0], a[1], a[2], a[3], mrt::V3{r.d.x, r.d.y, r.d.z})
-                            : nf_rho_node(nfl, tn);
-      node_test(a, r, kTmin, cull(), getenv("SLAB_NO_CONE") ? nf_rho_node(nfl, tn) : rho, h, e, x);
-      const uint32_t base = k & kNfIdx, right = base + 2 + ((a[3] >> 24) & 1u);
-      if (h[0] && h[1]) {
-        const bool lf = !(e[1] < e[0]);
-        stack.push_back(lf ? right : base);
-        stack_nl.push_back(lf ? x[1] : x[0]);
-        if (stack.size() > kNfStack) {
-          fprintf(stderr, "nf: stack overflow\n");
-          exit(3);
-        }
-        i = lf ? base : right;
-        nl = getenv("SLAB_NO_NL") ? INFINITY : (lf ? x[0] : x[1]);
-      } else if (h[0] || h[1]) {
-        i = h[0] ? base : right;
-        nl = getenv("SLAB_NO_NL") ? INFINITY : (h[0] ? x[0] : x[1]);
-      } else if (!pop()) {
-        break;
-      }
+  if (!t.done) trav_fetch(in, t);
+}
+
+// The reference's walk (k_trace's exact variant, one lane).
+template <uint32_t ALPHA>
+Hit walk_ref(const Scene& c, V o, V d, Stats* st = nullptr, bool check = false) {
+  OneRay p(c.S, o, d);
+  Trav t;
+  LocalCounters lc;
+  trav_init(p.in, t, 0, INFINITY);
+  while (!t.done) ref_step<ALPHA>(c, p.in, t, lc, st, check, o, d);
+  if (st) st->boxes += lc.node_visits, st->undecided += lc.box_exact;
+  return trav_hit(p.in, t);
+}
+
+// The verified near-first walk in the per-lane order of k_trace's NF variant:
+// the reference's steps once it has fallen back, the winner's check when the
+// walk is over, else a near-first step.
+template <uint32_t ALPHA>
+Hit walk_nf(const Scene& c, V o, V d, Stats& st, uint64_t& fallbacks, uint64_t& starts_ref) {
+  OneRay p(c.S, o, d);
+  const TravIn& in = p.in;
+  // two words beyond kNfStack: a step pushes at most two, so an overflow is
+  // seen after the step that made it instead of being written out of bounds
+  uint32_t words[kNfStack + 2];
+  const NfStack stk{words, 1};
+  Trav t;
+  LocalCounters lc;
+  trav_init(in, t, 0, INFINITY, c.S.nf_world);
+  if (t.sp == kExactMode) ++starts_ref;  // nf_start: the bound does not cover this ray
+  while (!t.done) {
+    if (t.sp == kExactMode) {
+      ref_step<ALPHA>(c, in, t, lc, &st, false, o, d);
       continue;
     }
-    uint32_t next;
-    if (k == KIND_TRI) {
-      float t;
-      const uint32_t pr = MRT_REF(MRT_REF_TRIANGLE, a[6] & kTriIdMask);
-      if (st) st->loads += 3, st->prims++;
-      if (tri_hit({f(a[0]), f(a[1]), f(a[2])}, {f(a[3]), f(a[4]), f(a[5])}, {f(a[8]), f(a[9]), f(a[10])}, r.o, r.d,
-                  kTmin, cull(), t))
-        hit(t, pr);
-      next = a[11];
-    } else if (k == KIND_SPHERE) {
-      float t;
-      const uint32_t pr = MRT_REF(MRT_REF_SPHERE, a[4]);
-      if (st) st->loads += 2, st->prims++;
-      if (sphere_hit({f(a[0]), f(a[1]), f(a[2])}, f(a[3]), r.o, r.d, kTmin, cull(), t)) hit(t, pr);
-      next = a[5];
-    } else if (k == KIND_INST && a[3] != 0 &&
-               !nf_wild_hit(wild_entry(s, a[3]), mrt::V3{r.o.x, r.o.y, r.o.z}, mrt::V3{r.d.x, r.d.y, r.d.z}, dot(r.d, r.d),
-                            kTmin, cull())) {
-      if (st) st->loads += 4, st->wild_skips++;  // path.h nf_wild_enter: the WILD entry, then the leaf's next
-      next = a[2];
-    } else if (k == KIND_INST || k == KIND_MODEL) {
-      if (st) st->loads += k == KIND_INST ? 5 : 2;
-      if (st && k == KIND_INST) st->entries++;
-      if (a[2] != kNfPop) stack.push_back(a[2]), stack_nl.push_back(nl);
-      stack.push_back(0x80000000u);
-      stack_nl.push_back(nl);
-      if (k == KIND_INST) {
-        const float* m = &s.inst_inv[12 * (size_t)a[0]];
-        r = make_ray(xf(m, wr.o, 1.0f), xf(m, wr.d, 0.0f), s.early_ok);
-        ret = (i + 2) | 0x80000000u;
-        margin();
+    if (t.sp == kNfDone) {
+      const uint32_t before = lc.node_visits;
+      nf_finish<true>(in, t, lc);
+      st.loads += 2 * (lc.node_visits - before);  // the reference boxes it tested
+      if (!t.done) trav_fetch(in, t);
+      continue;
+    }
+    const bool in_inst = t.ret != kNoRet && (t.ret & kRetInstance);
+    if (trav_at_box(t)) {
+      st.loads += 2;
+      trav_box_index_nf<true>(in, stk, t, lc);
+    } else {
+      const uint32_t kind = t.s1.w;
+      if (kind == KIND_TRI || kind == KIND_SPHERE) {
+        st.loads += kind == KIND_TRI ? 3 : 2;
+        st.prims++;
+      } else if (kind == KIND_INST && t.s0.w != 0 && !nf_wild_enter(in, t, t.s0.w)) {
+        st.loads += 4, st.wild_skips++;  // the WILD entry, then the leaf's next
+      } else if (kind == KIND_INST || kind == KIND_MODEL) {
+        st.loads += kind == KIND_INST ? 5 : 2;
+        if (kind == KIND_INST) st.entries++;
       } else {
-        ret = i + 2;
+        fprintf(stderr, "nf: unsupported kind %u at %u\n", kind, t.i);
+        exit(2);
       }
-      i = a[1];
-      continue;
-    } else {
-      fprintf(stderr, "nf: unsupported kind %u at %u\n", k, i);
-      exit(2);
+      trav_prim_index_nf<true, ALPHA>(in, stk, t, lc);
     }
-    if (next != kNfPop) {
-      i = next;
-    } else if (!pop()) {
-      break;
+    if (in_inst && t.ret == kNoRet) st.loads += 2;  // the step left an instance: the world ray again
+    if (t.sp != kNfDone && t.sp > kNfStack) {
+      fprintf(stderr, "nf: stack overflow\n");
+      exit(3);
     }
+    if (t.sp != kNfDone) trav_fetch(in, t);
   }
-  // the check: the winner's innermost reference ancestors pass at
-  // tau = min(t2, best * (1 + 2^-10)), a lower bound of the reference's t_max there
-  bool ok = true;
-  const float tau = fminf(t2, cull());
-  auto box_at = [&](uint32_t rec, const Ray& rr) {
-    const uint32_t* b = w + 4 * (size_t)rec;
-    float mn[3] = {f(b[0]), f(b[1]), f(b[2])}, mx[3] = {f(b[3]), f(b[4]), f(b[5])};
-    if (st) st->boxes++, st->loads += 2;
-    return box_exact(mn, mx, rr, kTmin, tau);
-  };
-  if (prim) {
-    const uint32_t kind = prim >> 28, id = prim & 0x0FFFFFFFu;
-    const uint32_t own = s.vnf_leaf[2 * (size_t)(s.vnf_base[kind == MRT_REF_SPHERE ? VNF_SPHERE : VNF_TRI] + id)];
-    if (hit_ret == ~0u) {
-      if (own != kNoParent) ok = box_at(own, wr);
-    } else {
-      const bool inst = (hit_ret & 0x80000000u) != 0;
-      const uint32_t cid = w[4 * (size_t)((hit_ret & 0x7FFFFFFFu) - 2)];
-      const uint32_t wpar = s.vnf_leaf[2 * (size_t)(s.vnf_base[inst ? VNF_INST : VNF_MODEL] + cid)];
-      if (wpar != kNoParent) ok = box_at(wpar, wr);
-      if (ok && own != kNoParent) {
-        Ray rr = wr;
-        if (inst) {
-          const float* m = &s.inst_inv[12 * (size_t)cid];
-          rr = make_ray(xf(m, wr.o, 1.0f), xf(m, wr.d, 0.0f), s.early_ok);
-        }
-        ok = box_at(own, rr);
-      }
-    }
-  }
-  if (ok) {
-    uint32_t cont = 0;
-    if (hit_ret != ~0u) {
-      const uint32_t rec = (hit_ret & 0x7FFFFFFFu) - 2;
-      cont = MRT_REF((hit_ret & 0x80000000u) ? MRT_REF_INSTANCE : MRT_REF_MODEL, w[4 * (size_t)rec]);
-    }
-    return {prim, cont, best};
-  }
-  ++*fallbacks;
-  return walk_plain(s, o, d, st);
+  st.boxes += lc.node_visits;
+  fallbacks += lc.vnf_fallbacks;
+  return trav_hit(in, t);
 }
 
-}  // namespace
+bool same_hit(const Hit& r, const Hit& q) {
+  return r.prim == q.prim && r.container == q.container && (r.prim == kRefNone || f2u(r.t) == f2u(q.t));
+}
 
-int main(int argc, char** argv) {
-  if (argc < 2) return 1;
-  const int n = argc > 2 ? atoi(argv[2]) : 20000;
-  mrt_builder* b = nullptr;
-  mrt_builder_new(1, &b);
-  if (mrt_builder_builtin(b, argv[1], 16.0f / 9.0f, argc > 3 ? argv[3] : "tests/golden") != 0) {
-    printf("%s: %s\n", argv[1], mrt_global_last_error());
-    return 1;
+// `hits` / `hits-nf`: k_rays_in -> walk -> k_rays_out on the host
+template <uint32_t ALPHA>
+int trace_file(const Scene& c, bool nf, const char* rays_path, const char* out_path) {
+  FILE* f = fopen(rays_path, "rb");
+  if (!f) return fprintf(stderr, "cannot read %s\n", rays_path), 1;
+  std::vector<float> rays;
+  float buf[6 * 1024];
+  for (size_t k; (k = fread(buf, sizeof(float), 6 * 1024, f)) > 0;) rays.insert(rays.end(), buf, buf + k);
+  fclose(f);
+  const size_t n = rays.size() / 6;
+  std::vector<uint32_t> out(4 * n);
+  Stats st;
+  uint64_t fb = 0, sr = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const float* r = &rays[6 * i];
+    const V o{r[0], r[1], r[2]}, d{r[3], r[4], r[5]};
+    const Hit h = nf ? walk_nf<ALPHA>(c, o, d, st, fb, sr) : walk_ref<ALPHA>(c, o, d);
+    const bool hit = h.prim != kRefNone;
+    out[4 * i] = h.prim;
+    out[4 * i + 1] = h.container;
+    out[4 * i + 2] = hit ? f2u(h.t) : 0u;
+    out[4 * i + 3] = hit && resolve_hit(c.S, o, d, h).front_face ? 1u : 0u;
   }
-  mrt_builder_build_bvh(b);
-  mrt_scene_desc d;
-  mrt_camera cam;
-  mrt_builder_desc(b, &d, &cam);
-  HostScene s;
-  s.keep_nf_boxes = true;  // the bound checks' leaf boxes
-  s.nf_build = kNfBuildAlways;  // the trees even where the per-scene rule would walk the reference's way
+  f = fopen(out_path, "wb");
+  if (!f || fwrite(out.data(), 4, out.size(), f) != out.size()) return fprintf(stderr, "cannot write %s\n", out_path), 1;
+  fclose(f);
+  return 0;
+}
+
+template <uint32_t ALPHA>
+int run(int argc, char** argv, const mrt_scene_desc& d, const mrt_camera& cam, HostScene& s) {
+  const int n = argc > 2 ? atoi(argv[2]) : 20000;
+  const char* mode = argc > 4 ? argv[4] : "";
   std::string err;
-  if (!build_host_scene(d, s, err)) {
-    printf("%s\n", err.c_str());
-    return 1;
+  const bool hits_nf = !strcmp(mode, "hits-nf");
+  if (hits_nf || !strcmp(mode, "hits")) {
+    if (argc < 7) return fprintf(stderr, "%s <rays.f32> <out.u32>\n", mode), 1;
+    if (hits_nf && !s.nf_ok) return fprintf(stderr, "%s: no near-first trees (%s)\n", argv[1], s.nf_note.c_str()), 1;
+    return trace_file<ALPHA>(Scene(s), hits_nf, argv[5], argv[6]);
   }
   // `layout` mode: the same rays through the plain preorder stream (build_host_scene(..., false))
   // and the default layout (BLAS regions with siblings together) must find the
   // same closest hits, t bits included, after the same number of box tests
   HostScene dfs;
-  const bool layout = argc > 4 && !strcmp(argv[4], "layout");
+  const bool layout = !strcmp(mode, "layout");
   // `nf` mode: the verified near-first walk must find the reference's closest
   // hits (primitive, container, t bits) on every ray
-  const bool nf = argc > 4 && (!strcmp(argv[4], "nf") || !strcmp(argv[4], "graze") || !strcmp(argv[4], "tangent"));
+  const bool nf = !strcmp(mode, "nf") || !strcmp(mode, "graze") || !strcmp(mode, "tangent");
   // `graze` mode: rays nearly parallel to a triangle of the scene (angle
   // 10^U(-8,-1.5) rad to its plane, through a random point of it, from 0.5-60
   // units back; through an instance's transform half the time) — where
   // Moller-Trumbore's t is least accurate, the near-first walk's culling
   // margin is tested hardest
-  const bool graze = argc > 4 && !strcmp(argv[4], "graze");
+  const bool graze = !strcmp(mode, "graze");
   // `tangent` mode: rays nearly tangent to a sphere (offset 10^U(-7,-1) of its
   // radius from the tangent line) from 1-400 radii away — where the sphere
   // test's disc cancels
-  const bool tangent = argc > 4 && !strcmp(argv[4], "tangent");
-  const bool stress = graze || tangent;
+  const bool tangent = !strcmp(mode, "tangent");
   if (getenv("SLAB_ZERO_RHO")) {  // experiment: the walk without its rounding margins (not exact)
     const float wr = s.nfb.wr;
     s.nfb = NfBound{};
@@ -658,6 +428,7 @@ int main(int argc, char** argv) {
              inst, e.mn[0], e.mn[1], e.mn[2], e.mx[0], e.mx[1], e.mx[2], e.a0, e.a1, e.b0, e.b1, e.r);
     }
   }
+  const Scene scn(s);  // after the experiments above: it carries s.nfb
   uint64_t nf_bad = 0, nf_fallbacks = 0, nf_starts_ref = 0, nf_even = 0, nf_odd = 0;
   BoundCheck bc;
   if (nf) g_bc = &bc;
@@ -666,6 +437,7 @@ int main(int argc, char** argv) {
   if (layout) {
     if (!build_host_scene(d, dfs, err, false)) return 1;
   }
+  const Scene scn_dfs(dfs);
   uint64_t layout_bad = 0;
   std::mt19937 g(7);
   std::uniform_real_distribution<float> u(0.0f, 1.0f);
@@ -706,7 +478,7 @@ int main(int argc, char** argv) {
       if (b1 + b2 > 1) b1 = 1 - b1, b2 = 1 - b2;
       const V p{A.x + (B.x - A.x) * b1 + (C.x - A.x) * b2, A.y + (B.y - A.y) * b1 + (C.y - A.y) * b2,
                 A.z + (B.z - A.z) * b1 + (C.z - A.z) * b2};
-      V nn = cross(sub(B, A), sub(C, A));
+      V nn = cross(B - A, C - A);
       const double nl = sqrt((double)dot(nn, nn));
       if (!(nl > 0)) continue;
       nn = {(float)(nn.x / nl), (float)(nn.y / nl), (float)(nn.z / nl)};
@@ -729,28 +501,22 @@ int main(int argc, char** argv) {
       ro = o;
       cam_d = rd;
     } else {  // from the first hit of the previous camera ray, random direction (a bounce)
-      const Result h = walk_plain(s, o, cam_d);
-      if (h.prim == 0) continue;
+      const Hit h = walk_ref<ALPHA>(scn, o, cam_d);
+      if (h.prim == kRefNone) continue;
       ro = {o.x + cam_d.x * h.t, o.y + cam_d.y * h.t, o.z + cam_d.z * h.t};
       rd = {u(g) * 2 - 1, u(g) * 2 - 1, u(g) * 2 - 1};
     }
-    fast += make_ray(ro, rd, s.early_ok).fast;
+    fast += tray_fast(make_tray(ro, rd, scn.S.fast_ok));
     const uint64_t boxes0 = st.boxes;
-    const Result r = walk_plain(s, ro, rd, &st);
-    hits += r.prim != 0;
+    const Hit r = walk_ref<ALPHA>(scn, ro, rd, &st, true);
+    hits += r.prim != kRefNone;
     if (nf) {
       const uint64_t nb0 = nf_st.boxes;
-      BoundCheck* keep = g_bc;
-      g_bc = nullptr;  // the reference walk inside walk_nf's fallback is not checked twice
-      const Result q = walk_nf(s, ro, rd, &nf_st, &nf_fallbacks, &nf_starts_ref);
-      g_bc = keep;
+      const Hit q = walk_nf<ALPHA>(scn, ro, rd, nf_st, nf_fallbacks, nf_starts_ref);
       nf_per_ray.push_back(uint32_t(nf_st.boxes - nb0));
       (k % 2 ? nf_odd : nf_even) += nf_st.boxes - nb0;
       ref_per_ray.push_back(uint32_t(st.boxes - boxes0));
-      uint32_t tb, qb;
-      memcpy(&tb, &r.t, 4);
-      memcpy(&qb, &q.t, 4);
-      const bool bad = r.prim != q.prim || r.container != q.container || (r.prim && tb != qb);
+      const bool bad = !same_hit(r, q);
       if (bad && nf_bad < 5)
         fprintf(stderr, "nf differs: ref prim %08x cont %08x t %a | nf prim %08x cont %08x t %a\n", r.prim, r.container,
                 r.t, q.prim, q.container, q.t);
@@ -758,11 +524,8 @@ int main(int argc, char** argv) {
     }
     if (layout) {
       Stats sd;
-      const Result q = walk_plain(dfs, ro, rd, &sd);
-      uint32_t tb, qb;
-      memcpy(&tb, &r.t, 4);
-      memcpy(&qb, &q.t, 4);
-      layout_bad += r.prim != q.prim || r.container != q.container || tb != qb || sd.boxes != st.boxes - boxes0;
+      const Hit q = walk_ref<ALPHA>(scn_dfs, ro, rd, &sd);
+      layout_bad += r.prim != q.prim || r.container != q.container || f2u(r.t) != f2u(q.t) || sd.boxes != st.boxes - boxes0;
     }
   }
   if (nf) {
@@ -803,6 +566,38 @@ int main(int argc, char** argv) {
   printf("%-14s rays %d (early domain %llu) hits %llu  boxes %llu  left to the exact test %.5f  wrong %llu\n", argv[1],
          n, (unsigned long long)fast, (unsigned long long)hits, (unsigned long long)st.boxes,
          (double)st.undecided / std::max<uint64_t>(st.boxes, 1), (unsigned long long)st.wrong);
-  mrt_builder_free(b);
   return st.wrong ? 1 : 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  if (argc < 2) return 1;
+  mrt_builder* b = nullptr;
+  mrt_builder_new(1, &b);
+  if (mrt_builder_builtin(b, argv[1], 16.0f / 9.0f, argc > 3 ? argv[3] : "tests/golden") != 0) {
+    printf("%s: %s\n", argv[1], mrt_global_last_error());
+    return 1;
+  }
+  mrt_builder_build_bvh(b);
+  mrt_scene_desc d;
+  mrt_camera cam;
+  mrt_builder_desc(b, &d, &cam);
+  HostScene s;
+  s.keep_nf_boxes = true;  // the bound checks' leaf boxes
+  s.nf_build = kNfBuildAlways;  // the trees even where the per-scene rule would walk the reference's way
+  std::string err;
+  if (!build_host_scene(d, s, err)) {
+    printf("%s\n", err.c_str());
+    return 1;
+  }
+  if (s.trav_rng) {  // Volume, Mix alpha tests: the walks here carry no random stream
+    printf("%s: the scene's traversal draws random numbers; not supported\n", argv[1]);
+    return 2;
+  }
+  // alpha tests the way the library chooses its k_trace variant (trace.hip launch_trace)
+  const bool ext = !s.surf_ops.empty() || s.bg_kind == MRT_BG_CUBEMAP;
+  const int rc = !s.has_alpha ? run<0>(argc, argv, d, cam, s) : ext ? run<2>(argc, argv, d, cam, s) : run<1>(argc, argv, d, cam, s);
+  mrt_builder_free(b);
+  return rc;
 }
