@@ -17,16 +17,34 @@ struct Surf {
   uint32_t material;
 };
 
+// A loaded value pinned where it was loaded: the compiler otherwise sinks a
+// load to the block of its first use, behind the waits in between (a
+// sphere's material index went out only after its centre had arrived and the
+// normal's divisions had run). Generates no instruction.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MRT_PIN_LOAD(x) asm volatile("" : "+v"(x))
+#else
+#define MRT_PIN_LOAD(x) (void)0
+#endif
+
 MRT_HD Surf resolve_hit(const DevScene& S, V3 o, V3 d, const Hit& h) {
   Surf s;
   V3 ro = o, rd = d;
   const uint32_t ckind = h.container >> 28, cidx = h.container & 0x0FFFFFFFu;
   V3 f0, f1, f2, f3;
+  // the container's override material goes out with the first gather of the
+  // hit (the instance's inverse, the triangle's quads), not behind the last.
+  // (inst_fwd stays behind the barycentrics: held through them, its 12
+  // registers put 24 B of k_shade's 7-waves variant into scratch.)
+  uint32_t over = MRT_NO_MATERIAL;
   if (ckind == MRT_REF_INSTANCE) {
     V3 c0, c1, c2, c3;
+    over = S.inst_mat[MRT_IDX(S, cidx, S.n_inst, 12)];
     load_m12(S.inst_inv + (size_t)MRT_IDX(S, cidx, S.n_inst, 9) * 12, c0, c1, c2, c3);
     ro = xform(c0, c1, c2, c3, o, 1.0f);
     rd = xform(c0, c1, c2, c3, d, 0.0f);
+  } else if (ckind == MRT_REF_MODEL) {
+    over = S.model_mat[MRT_IDX(S, cidx, S.n_models, 13)];
   }
   const uint32_t pkind = h.prim >> 28, pidx = h.prim & 0x0FFFFFFFu;
   V3 outward;
@@ -43,10 +61,11 @@ MRT_HD Surf resolve_hit(const DevScene& S, V3 o, V3 d, const Hit& h) {
     const uint32_t sp = MRT_IDX(S, pidx, S.n_sph, 10);
     V3 c = ld3(S.sph + (size_t)sp * 4);
     float r = S.sph[(size_t)sp * 4 + 3];
+    s.material = S.sph_mat[sp];  // with {c, r}: one wait for both
+    MRT_PIN_LOAD(s.material);
     outward = (s.point - c) / r;
     s.has_uv = false;
     s.uv = V2{0, 0};
-    s.material = S.sph_mat[sp];
   } else {
     TriShade t = load_tri(S, pidx);
     float a0, a1, a2;
@@ -63,12 +82,8 @@ MRT_HD Surf resolve_hit(const DevScene& S, V3 o, V3 d, const Hit& h) {
     load_m12(S.inst_fwd + (size_t)MRT_IDX(S, cidx, S.n_inst, 11) * 12, f0, f1, f2, f3);
     s.point = xform(f0, f1, f2, f3, s.point, 1.0f);
     s.normal = unit(xform(f0, f1, f2, f3, s.normal, 0.0f));
-    uint32_t m = S.inst_mat[MRT_IDX(S, cidx, S.n_inst, 12)];
-    if (m != MRT_NO_MATERIAL) s.material = m;
-  } else if (ckind == MRT_REF_MODEL) {
-    uint32_t m = S.model_mat[MRT_IDX(S, cidx, S.n_models, 13)];
-    if (m != MRT_NO_MATERIAL) s.material = m;
   }
+  if (over != MRT_NO_MATERIAL) s.material = over;
   return s;
 }
 
@@ -167,47 +182,77 @@ MRT_DEV V3 background(const DevScene& S, V3 d, LocalCounters& lc) {
 
 // Hit::emit + Hit::scatter (geom.rs:26-32). Returns true when the path
 // continues with (new_o, new_d) and attenuation `atten`.
+//
+// The head of a material record, q0 and q1 of GpuMaterial (layout.h): what
+// every kind reads, two 16-B loads issued together. q2 (left, right,
+// surf_len) is read only where a Mix or a composite surface needs it.
+struct MatHead {
+  uint32_t kind, surf_kind, texture;
+  float param;
+  float color[4];
+};
+MRT_DEV MatHead load_mat_head(const DevScene& S, uint32_t mi) {
+  const GpuMaterial* p = S.materials + MRT_IDX(S, mi, S.n_materials, 4);
+  return MatHead{p->kind, p->surf_kind, p->texture, p->param, {p->color[0], p->color[1], p->color[2], p->color[3]}};
+}
 // Mix::scatter/emit/alpha_test (material.rs:402-424): every call draws once
 // to pick a side, recursively; children precede their Mix in the table.
-MRT_DEV uint32_t mix_pick(const DevScene& S, uint32_t mi, PathRng& rng) {
-  for (;;) {
-    const GpuMaterial m = S.materials[MRT_IDX(S, mi, S.n_materials, 4)];
-    if (m.kind != MRT_MAT_MIX) return mi;
-    mi = rng.f32() < m.param ? m.left : m.right;
+// `m` is the head of record `mi` (the caller's register copy of the hit's
+// root record): a material that is no Mix draws nothing and loads nothing.
+// Returns the picked record's index, its head in `m`.
+MRT_DEV uint32_t mix_pick(const DevScene& S, uint32_t mi, MatHead& m, PathRng& rng) {
+  while (m.kind == MRT_MAT_MIX) {
+    const GpuMaterial* p = S.materials + MRT_IDX(S, mi, S.n_materials, 4);
+    const uint32_t left = p->left, right = p->right;
+    mi = rng.f32() < m.param ? left : right;
+    m = load_mat_head(S, mi);
   }
+  return mi;
+}
+template <bool EXT>
+MRT_DEV V4 mat_get_f(const DevScene& S, const MatHead& m, uint32_t mi, V2 uv, LocalCounters& lc) {
+  uint32_t len = 0;
+  if (EXT && m.surf_kind == SURF_PROGRAM) len = S.materials[MRT_IDX(S, mi, S.n_materials, 4)].surf_len;
+  return surface_ref_get_f<EXT>(S, m.surf_kind, m.texture, len, m.color, uv, lc);
 }
 
 // Lambertian::scatter (material.rs:203-215)
 template <bool EXT>
-MRT_DEV void lambertian(const DevScene& S, const GpuMaterial& m, const Surf& s, PathRng& rng, V3& atten, V3& new_d,
-                        LocalCounters& lc) {
+MRT_DEV void lambertian(const DevScene& S, const MatHead& m, uint32_t mi, const Surf& s, PathRng& rng, V3& atten,
+                        V3& new_d, LocalCounters& lc) {
   V3 dir = s.normal + unit(random_in_unit_sphere(rng));
   if (near_zero(dir)) dir = s.normal;
-  V4 c = surface_get_f<EXT>(S, m, uv_or_zero(s.has_uv, s.uv), lc);
+  V4 c = mat_get_f<EXT>(S, m, mi, uv_or_zero(s.has_uv, s.uv), lc);
   atten = V3{c.x, c.y, c.z};
   new_d = dir;
 }
 
 // Hit::emit then Hit::scatter (world.rs:69-70), in that order of RNG draws.
+// The hit's root record is fetched once; the emit pick and the scatter pick
+// both start from that copy. root_kind: its kind (k_shade's survivor key).
 template <bool EXT>
 MRT_DEV bool scatter(const DevScene& S, const Surf& s, V3 d, PathRng& rng, V3& emitted, V3& atten, V3& new_d,
-                     LocalCounters& lc) {
+                     LocalCounters& lc, uint32_t& root_kind) {
+  const MatHead root = load_mat_head(S, s.material);
+  root_kind = root.kind;
   emitted = V3{0, 0, 0};
   {
-    const GpuMaterial e = S.materials[mix_pick(S, s.material, rng)];
+    MatHead e = root;
+    mix_pick(S, s.material, e, rng);
     if (e.kind == MRT_MAT_DIFFUSE_LIGHT) emitted = V3{e.color[0], e.color[1], e.color[2]};
   }
-  const GpuMaterial m = S.materials[mix_pick(S, s.material, rng)];
+  MatHead m = root;
+  const uint32_t mi = mix_pick(S, s.material, m, rng);
   V2 uv = uv_or_zero(s.has_uv, s.uv);
   switch (m.kind) {
     case MRT_MAT_LAMBERTIAN:
-      lambertian<EXT>(S, m, s, rng, atten, new_d, lc);
+      lambertian<EXT>(S, m, mi, s, rng, atten, new_d, lc);
       return true;
     case MRT_MAT_METAL: {
       V3 reflected = reflect(unit(d), s.normal);
       V3 dir = reflected + (random_in_unit_sphere(rng) * m.param);
       if (dot(dir, s.normal) > 0.0f) {
-        V4 c = surface_get_f<EXT>(S, m, uv, lc);
+        V4 c = mat_get_f<EXT>(S, m, mi, uv, lc);
         atten = V3{c.x, c.y, c.z};
         new_d = dir;
         return true;
@@ -224,7 +269,7 @@ MRT_DEV bool scatter(const DevScene& S, const Surf& s, V3 d, PathRng& rng, V3& e
       if (cannot_refract || reflectance(cos_theta, ratio) > rng.f32()) {
         new_d = reflect(ud, s.normal);
       } else if (m.kind == MRT_MAT_SPECULAR) {
-        lambertian<EXT>(S, m, s, rng, atten, new_d, lc);  // return self.inner.scatter(ray, hit)
+        lambertian<EXT>(S, m, mi, s, rng, atten, new_d, lc);  // return self.inner.scatter(ray, hit)
         return true;
       } else {
         new_d = refract(ud, s.normal, ratio);

@@ -145,7 +145,8 @@ __global__ __launch_bounds__(kBlock) void k_prepass(DevScene S, DevCamera cam, u
   if (h.prim != kRefNone) {
     Surf s = resolve_hit(S, o, d, h);
     V3 emitted, atten, nd;
-    a = scatter<EXT>(S, s, d, rng, emitted, atten, nd, lc) ? atten : emitted;
+    uint32_t mkind;
+    a = scatter<EXT>(S, s, d, rng, emitted, atten, nd, lc, mkind) ? atten : emitted;
     n = s.normal;
   } else {
     a = background<EXT>(S, d, lc);

@@ -114,12 +114,13 @@ __global__ __launch_bounds__(kBlock) void k_refill(DevCamera cam, RenderParams r
   for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < mv; j += gridDim.x * kBlock) {
     // sources [cap - mv, cap) and destinations [lo + m, lo + m + mv) are disjoint
     const uint32_t a = src + j, b = dst + j;
-    const float4 thr = out.thr[a];
-    out.ro[b] = out.ro[a];
-    out.rd[b] = out.rd[a];
+    const float4 thr = out.thr[a], ro = out.ro[a], rd = out.rd[a];
+    const uint4 rs = out.rng[a];
+    out.ro[b] = ro;
+    out.rd[b] = rd;
     out.thr[b] = thr;
+    out.rng[b] = rs;
     if (holds_l(thr)) out.rad[b] = out.rad[a];
-    out.rng[b] = out.rng[a];
   }
   for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < m; j += gridDim.x * kBlock) {
     float4 ro, rd;
@@ -136,8 +137,8 @@ __global__ __launch_bounds__(kBlock) void k_refill(DevCamera cam, RenderParams r
 // k_shade only shades and compacts: new camera rays go in behind the
 // survivors (k_reserve + k_refill). (Round 3's in-place regeneration of
 // finished slots is profiles/r3_experiments/ab_branches.patch.)
-// WPE: waves per SIMD the register budget is sized for (8: 64 VGPRs, 32 B of
-// scratch; 7: 71 VGPRs, none). With 8, k_shade takes more of the CU beside
+// WPE: waves per SIMD the register budget is sized for (8: 64 VGPRs, 16 B of
+// scratch; 7: 68 VGPRs, none). With 8, k_shade takes more of the CU beside
 // the other queue's k_trace; a world whose records stream from the Infinity
 // Cache runs better with 7 (mesh_ply 948.6 -> 969.0, 6: 962.9 Msamples/s),
 // an L2-resident one with 8 (sphere_grid 808.8, 7: 778.1, 6: 761.0;
@@ -165,21 +166,23 @@ __global__ __launch_bounds__(kShadeBlock, WPE) void k_shade(DevScene S, RenderPa
     bool alive = false;
     float4 ro{}, rd{}, thr{}, rad{};
     uint4 rs{};
-    uint32_t mat = kShadeIdle;
+    uint32_t mat = kShadeIdle, mkind = 0;
     if (i < n) {
       nshaded += 1;
+      // the lane's own slot in one batch, the hit first: the primitive's
+      // gather goes out on it while the state is still in flight
+      const uint4 hv = hits[i];
+      thr = in.thr[i];
       ro = in.ro[i];
       rd = in.rd[i];
-      thr = in.thr[i];
-      if (holds_l(thr)) rad = in.rad[i];
       rs = in.rng[i];
-      const uint4 hv = hits[i];
+      if (holds_l(thr)) rad = in.rad[i];
       Hit h{__uint_as_float(hv.x), hv.y, hv.z};
       V3 o{ro.x, ro.y, ro.z}, d{rd.x, rd.y, rd.z}, T{thr.x, thr.y, thr.z}, L{rad.x, rad.y, rad.z};
       uint32_t g = __float_as_uint(ro.w), k = __float_as_uint(rd.w);
       PathRng rng{(unsigned long long)rs.x | ((unsigned long long)rs.y << 32),
                   (unsigned long long)rs.z | ((unsigned long long)rs.w << 32)};
-      const bool cont = shade_step<EXT>(S, rp.max_depth, h, o, d, T, L, k, rng, lc, nbounce, mat);
+      const bool cont = shade_step<EXT>(S, rp.max_depth, h, o, d, T, L, k, rng, lc, nbounce, mat, mkind);
       if (cont) {
         alive = true;
         ro = make_float4(o.x, o.y, o.z, __uint_as_float(g));
@@ -194,13 +197,14 @@ __global__ __launch_bounds__(kShadeBlock, WPE) void k_shade(DevScene S, RenderPa
         nsample += 1;
       }
     }
-    if (COUNT) shade_coherence(S, mat, lc);
+    if (COUNT) shade_coherence(mat, mkind, lc);
     // compact the survivors into the next pool: one atomic per workgroup
     // (same-address atomics from every wave serialise in L2)
     uint32_t slot;
     if (rp.shade_bin) {  // survivors grouped by the material kind they scattered from (wg_reserve_keyed)
-      // key: the material kind scattered from and the signs of the new ray's y and x
-      const uint32_t kind = alive ? (S.materials[MRT_IDX(S, mat, S.n_materials, 4)].kind & 7u) : 0u;
+      // key: the material kind scattered from (the hit's own record's, as
+      // shade_step read it: no load here) and the signs of the new ray's y and x
+      const uint32_t kind = alive ? (mkind & 7u) : 0u;
       if (rp.shade_bin == 2) {  // y sign: the two ends of the pool; kind and x, z signs within
         const uint32_t key = (rd.y < 0.0f ? 32u : 0u) + kind * 4u + (rd.x < 0.0f ? 2u : 0u) + (rd.z < 0.0f ? 1u : 0u);
         slot = wg_reserve_keyed(&ctrl->active[cur ^ 1], alive, key, s_hist, &ctrl->surv[cur ^ 1], rp.pool_cap);
@@ -274,11 +278,11 @@ __global__ __launch_bounds__(kBlock) void k_render(DevScene S, DevCamera cam, Re
           float4 ro, rd;
           uint4 rs;
           if (ADOPT) {  // a wavefront path: {o, g} {d, bounces} T L rng (PathBufs)
+            const float4 tv = pool.thr[w];  // one batch; rad, rare, behind it
             ro = pool.ro[w];
             rd = pool.rd[w];
-            const float4 tv = pool.thr[w];
-            const float4 lv = holds_l(tv) ? pool.rad[w] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             rs = pool.rng[w];
+            const float4 lv = holds_l(tv) ? pool.rad[w] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             g = __float_as_uint(ro.w);
             k = __float_as_uint(rd.w);
             T = V3{tv.x, tv.y, tv.z};
@@ -317,8 +321,8 @@ __global__ __launch_bounds__(kBlock) void k_render(DevScene S, DevCamera cam, Re
         nh += h.prim != kRefNone;
         const float4 o4 = slot_ro[slot], d4 = slot_rd[slot];
         V3 o{o4.x, o4.y, o4.z}, d{d4.x, d4.y, d4.z};
-        uint32_t mat;
-        if (shade_step<false>(S, rp.max_depth, h, o, d, T, L, k, rng, lc, nbounces, mat)) {
+        uint32_t mat, mkind;
+        if (shade_step<false>(S, rp.max_depth, h, o, d, T, L, k, rng, lc, nbounces, mat, mkind)) {
           slot_ro[slot] = make_float4(o.x, o.y, o.z, 0.0f);
           slot_rd[slot] = make_float4(d.x, d.y, d.z, 0.0f);
           trav_init(tin, t, slot, INFINITY);

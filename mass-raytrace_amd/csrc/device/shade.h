@@ -12,11 +12,13 @@ using namespace mrt;
 // scatter that continues (and depth left) moves (o, d) to the scattered ray,
 // multiplies T by the attenuation and returns true.
 // (mat: the hit's material index, kShadeMiss for a miss: the counting
-// k_shade's coherence counters)
+// k_shade's coherence counters; mkind: that material's own kind — a Mix's is
+// Mix, not the picked leaf's — from the record scatter() fetched: k_shade's
+// survivor key)
 constexpr uint32_t kShadeMiss = 0xFFFFFFFEu, kShadeIdle = 0xFFFFFFFFu;
 template <bool EXT>
 MRT_DEV bool shade_step(const DevScene& S, uint32_t max_depth, const Hit& h, V3& o, V3& d, V3& T, V3& L, uint32_t& k,
-                        PathRng& rng, LocalCounters& lc, uint32_t& nbounce, uint32_t& mat) {
+                        PathRng& rng, LocalCounters& lc, uint32_t& nbounce, uint32_t& mat, uint32_t& mkind) {
   if (h.prim == kRefNone) {
     mat = kShadeMiss;
     L = L + T * background<EXT>(S, d, lc);
@@ -25,7 +27,7 @@ MRT_DEV bool shade_step(const DevScene& S, uint32_t max_depth, const Hit& h, V3&
   Surf s = resolve_hit(S, o, d, h);
   mat = s.material;
   V3 emitted, atten, nd;
-  bool cont = scatter<EXT>(S, s, d, rng, emitted, atten, nd, lc);
+  bool cont = scatter<EXT>(S, s, d, rng, emitted, atten, nd, lc, mkind);
   L = L + T * emitted;
   if (!cont) return false;
   T = T * atten;
@@ -42,10 +44,10 @@ MRT_DEV bool shade_step(const DevScene& S, uint32_t max_depth, const Hit& h, V3&
 // more kind: the background branch) — the branches the wave executes one
 // after another — and the distinct material indices (the material records
 // it gathers). A material-sorted pool could bring both to ~1.
-MRT_DEV void shade_coherence(const DevScene& S, uint32_t mat, LocalCounters& lc) {
+MRT_DEV void shade_coherence(uint32_t mat, uint32_t mkind, LocalCounters& lc) {
   const unsigned long long act = __ballot(mat != kShadeIdle);
   if (act == 0) return;
-  const uint32_t kind = mat == kShadeIdle ? 0xFFu : mat == kShadeMiss ? 16u : S.materials[MRT_IDX(S, mat, S.n_materials, 4)].kind;
+  const uint32_t kind = mat == kShadeIdle ? 0xFFu : mat == kShadeMiss ? 16u : mkind;
   uint32_t nk = 0, nm = 0;
   for (uint32_t kk = 0; kk <= 16; ++kk) nk += __ballot(kind == kk) != 0;
   for (unsigned long long rem = act; rem;) {
