@@ -176,6 +176,24 @@ impl Context {
         self.check(unsafe { mrt_tonemap(self.raw, w, h, rgb.as_ptr(), bounces.as_ptr(), passes, mode, out.as_mut_ptr()) })
     }
 
+    /// The Denoise view's guided filter on host buffers (mrt_denoise): colour
+    /// sums of `passes` passes, optionally the pre-pass (albedo, normal), ->
+    /// filtered colour (w*h*3). Its bytes: `tonemap(.., passes = 1, MRT_DISPLAY_DEFAULT)`.
+    pub fn denoise(&mut self, w: u32, h: u32, rgb: &[f32], passes: u32, aux: Option<(&[f32], &[f32])>,
+                   params: Option<&mrt_denoise_params>, out: &mut [f32]) -> Result<(), MrtError> {
+        let n = (w * h * 3) as usize;
+        assert!(rgb.len() >= n && out.len() >= n);
+        let (a, nrm) = match aux {
+            Some((a, nrm)) => {
+                assert!(a.len() >= n && nrm.len() >= n);
+                (a.as_ptr(), nrm.as_ptr())
+            }
+            None => (std::ptr::null(), std::ptr::null()),
+        };
+        let p = params.map_or(std::ptr::null(), |p| p as *const mrt_denoise_params);
+        self.check(unsafe { mrt_denoise(self.raw, w, h, rgb.as_ptr(), passes, a, nrm, p, out.as_mut_ptr()) })
+    }
+
     /// A tuning option of the context (mrt_set_option; names in massrt.h).
     pub fn set_option(&mut self, name: &str, value: i64) -> Result<(), MrtError> {
         let c = CString::new(name).expect("option name without NUL");
@@ -250,7 +268,16 @@ impl<'a> GpuImage<'a> {
         Ok(passes)
     }
 
+    /// The filter of the Denoise view (`None`: the defaults, which a new image has).
+    pub fn set_denoise(&mut self, params: Option<&mrt_denoise_params>) -> Result<(), MrtError> {
+        let p = params.map_or(std::ptr::null(), |p| p as *const mrt_denoise_params);
+        self.ctx.check(unsafe { mrt_image_set_denoise(self.raw, p) })
+    }
+
     /// Image::to_rgb_bytes + dump's row flip (main.rs:640-722, 763-766): w*h*3 bytes.
+    /// `mode` is one of MRT_DISPLAY_*; MRT_DISPLAY_DENOISE — what
+    /// `image.dump(path, DisplayMode::Denoise)` shows (main.rs:121-127) —
+    /// filters the sums with the image's pre-pass (colour-only before one).
     pub fn tonemap(&mut self, mode: u32, out: &mut [u8]) -> Result<(), MrtError> {
         assert!(out.len() >= (self.width * self.height * 3) as usize);
         self.ctx.check(unsafe { mrt_image_tonemap(self.raw, mode, out.as_mut_ptr()) })

@@ -69,6 +69,9 @@ pub const MRT_DISPLAY_DEFAULT: u32 = 0;
 pub const MRT_DISPLAY_DEPTH: u32 = 1;
 pub const MRT_DISPLAY_ALBEDO: u32 = 2;
 pub const MRT_DISPLAY_NORMAL: u32 = 3;
+/// DisplayMode::Denoise (main.rs:675-683): `mrt_image_tonemap` only; the
+/// filter itself is `mrt_denoise*` (massrt.h states it).
+pub const MRT_DISPLAY_DENOISE: u32 = 4;
 
 // ---- flat scene description (the reference tree) -------------------------
 
@@ -306,6 +309,16 @@ pub const MRT_TRAVERSAL_AUTO: i64 = -1;
 pub const MRT_TRAVERSAL_REFERENCE: i64 = 0;
 pub const MRT_TRAVERSAL_NEAR_FIRST: i64 = 1;
 
+/// The guided filter's parameters (mrt_denoise_default_params: 5, 2.0, 0.3, 0.6).
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct mrt_denoise_params {
+    pub iterations: u32,
+    pub sigma_color: f32,
+    pub sigma_albedo: f32,
+    pub sigma_normal: f32,
+}
+
 /// Opaque handles.
 #[repr(C)]
 pub struct mrt_ctx {
@@ -428,6 +441,14 @@ extern "C" {
                               d_normal: *mut f32, hip_stream: *mut c_void) -> i32;
     pub fn mrt_prepass(ctx: *mut mrt_ctx, width: u32, height: u32, seed: u64, albedo: *mut f32, normal: *mut f32)
         -> i32;
+    pub fn mrt_denoise_default_params(out: *mut mrt_denoise_params) -> i32;
+    pub fn mrt_denoise_device(ctx: *mut mrt_ctx, width: u32, height: u32, d_accum_rgb: *const f32, passes: u32,
+                              d_albedo: *const f32, d_normal: *const f32, params: *const mrt_denoise_params,
+                              d_out_rgb: *mut f32, hip_stream: *mut c_void) -> i32;
+    pub fn mrt_denoise(ctx: *mut mrt_ctx, width: u32, height: u32, accum_rgb: *const f32, passes: u32,
+                       albedo: *const f32, normal: *const f32, params: *const mrt_denoise_params, out_rgb: *mut f32)
+        -> i32;
+    pub fn mrt_image_set_denoise(img: *mut mrt_image, params: *const mrt_denoise_params) -> i32;
     pub fn mrt_display_gamma_thresholds(out256: *mut u32) -> i32;
     pub fn mrt_write_png(path: *const c_char, width: u32, height: u32, rgb8: *const u8) -> i32;
 

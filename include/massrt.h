@@ -492,7 +492,12 @@ int mrt_image_read(mrt_image* img, float* rgb, uint32_t* bounces, uint32_t* pass
  * queued work has ended */
 int mrt_image_gather(mrt_image* img);
 /* Image::to_rgb_bytes + dump's row flip (as mrt_tonemap) on devices[0]: W*H*3
- * bytes, top row first. ALBEDO / NORMAL show the pre-pass (zeros before one). */
+ * bytes, top row first. ALBEDO / NORMAL show the pre-pass (zeros before one).
+ * MRT_DISPLAY_DENOISE (image.dump(.., DisplayMode::Denoise), main.rs:121-127):
+ * the sums gathered as for Default, filtered on devices[0] (mrt_denoise_device)
+ * with the image's pre-pass buffers if mrt_image_prepass ran and colour-only
+ * otherwise, with the parameters of mrt_image_set_denoise, then Default's
+ * bytes; pass count 0 gives zeros. */
 int mrt_image_tonemap(mrt_image* img, uint32_t mode, uint8_t* rgb8);
 /* bytes that crossed between devices in the image's gathers, and their time */
 int mrt_image_gather_stats(mrt_image* img, uint64_t* bytes, double* ms);
@@ -601,6 +606,60 @@ int mrt_tonemap(mrt_ctx* ctx, uint32_t width, uint32_t height, const float* accu
 int mrt_prepass_device(mrt_ctx* ctx, uint32_t width, uint32_t height, uint64_t seed, float* d_albedo, float* d_normal,
                        void* hip_stream);
 int mrt_prepass(mrt_ctx* ctx, uint32_t width, uint32_t height, uint64_t seed, float* albedo, float* normal);
+/* ---- DisplayMode::Denoise (main.rs:675-683, 724-747) ---------------------
+ * The reference hands the LDR colour, the pre-pass albedo and the pre-pass
+ * normal to Intel OIDN and maps the result to bytes as Default does. OIDN is
+ * a neural filter; in its place stands a deterministic guided a-trous filter
+ * (Dammertz et al. 2010) with the same call shape, specified so tightly that
+ * the device result equals a host restatement bit for bit. With the
+ * reference's default build (feature `denoise` off) denoise() is a no-op and
+ * Denoise equals Default: here that is iterations = 0.
+ * IEEE f32 only (+ - * /, comparisons), no contraction, in this order.
+ * Pixel p = y*W + x, y = 0 the bottom row, as the accumulation buffers.
+ *   colour  v = (1.0f/(float)passes) * sum; c0 = (!(v >= 0) || v > 1) ? 1 : v
+ *           (the Default byte's own domain rule, so the byte of c0 is
+ *           Default's byte for every input)
+ *   albedo  a = p.min(1).max(0) (Rust min/max: NaN -> 1); normal n as stored
+ *   iteration i = 0 .. iterations-1, step s = 1 << i: for dy = -2..2 (outer),
+ *   dx = -2..2 (inner), q = (x + dx*s, y + dy*s); a tap outside the image is
+ *   skipped; k = h[|dx|] * h[|dy|], h = {3/8, 1/4, 1/16}; the centre tap has
+ *   w = k; every other tap
+ *     w = ((k * fall(e(c_i) * inv_c_i)) * fall(e(a) * inv_a)) * fall(e(n) * inv_n)
+ *     e(u) = (d.x*d.x + d.y*d.y) + d.z*d.z, d = u[q] - u[p]
+ *     fall(t) = t < 1 ? (1 - t)*(1 - t) : 0        (NaN -> 0)
+ *   acc.ch += w * c_i[q].ch; sw += w; then c_{i+1}[p].ch = acc.ch / sw.
+ *   inv_c_i = 1.0f / (s_i * s_i), s_i = sigma_color * 2^-i (the colour width
+ *   halves per iteration); inv_a, inv_n likewise from sigma_albedo and
+ *   sigma_normal, the same in every iteration; all computed on the host in
+ *   f32. A sigma <= 0 switches its term off (fall = 1). Without albedo and
+ *   normal buffers (both NULL; main.rs:737-743) those two terms are off.
+ * Output: c_iterations, W*H*3 f32 in the same pixel order; passes == 0 gives
+ * zeros. The bytes follow from mrt_tonemap*(.., passes = 1,
+ * MRT_DISPLAY_DEFAULT) on the output (exact: 1.0f * x == x); mrt_tonemap*
+ * itself has no albedo/normal inputs and rejects MRT_DISPLAY_DENOISE.
+ * Defaults: 5 iterations, sigma_color 2.0, sigma_albedo 0.3, sigma_normal
+ * 0.6 — for low sample counts (about 4-16 spp: relative L2 error x 0.35-0.69
+ * on cornell and sphere_grid); from about 64 spp on they over-smooth, lower
+ * sigma_color there. MRT_ERR_INVALID: zero width or height, iterations > 8,
+ * a NaN sigma, a null colour or output pointer, only one of albedo/normal,
+ * an output pointer equal to an input pointer. _device: device pointers,
+ * everything enqueued on `hip_stream` without a host wait; the working
+ * buffers (64 B per pixel) belong to the context, grow on demand and are
+ * reused, so calls on one context are ordered by the caller. */
+#define MRT_DISPLAY_DENOISE 4u
+typedef struct {
+  uint32_t iterations;
+  float sigma_color, sigma_albedo, sigma_normal;
+} mrt_denoise_params;
+int mrt_denoise_default_params(mrt_denoise_params* out);
+int mrt_denoise_device(mrt_ctx* ctx, uint32_t width, uint32_t height, const float* d_accum_rgb, uint32_t passes,
+                       const float* d_albedo, const float* d_normal, const mrt_denoise_params* params,
+                       float* d_out_rgb, void* hip_stream);
+int mrt_denoise(mrt_ctx* ctx, uint32_t width, uint32_t height, const float* accum_rgb, uint32_t passes,
+                const float* albedo, const float* normal, const mrt_denoise_params* params, float* out_rgb);
+/* The parameters mrt_image_tonemap(img, MRT_DISPLAY_DENOISE, ..) filters with
+ * (NULL: the defaults, which a new image has). */
+int mrt_image_set_denoise(mrt_image* img, const mrt_denoise_params* params);
 /* The 256 Default-mode thresholds (t[k] = f32 bits of the smallest x in
  * [0, 1] whose byte is >= k), derived from the host libm powf. */
 int mrt_display_gamma_thresholds(uint32_t* out256);

@@ -156,6 +156,7 @@ int mrt_destroy(mrt_ctx* c) {
   hipFree(c->d_acc_b);
   hipFree(c->d_rays);
   hipFree(c->d_rhits);
+  hipFree(c->dn_mem);
   hipFree(c->slot_ro);
   for (auto& kv : c->pixlists) hipFree(kv.second.first);
   if (c->tev[0]) hipEventDestroy(c->tev[0]);

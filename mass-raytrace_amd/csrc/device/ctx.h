@@ -111,6 +111,9 @@ struct mrt_ctx {
   float* d_rays = nullptr;
   uint4* d_rhits = nullptr;
   size_t rays_cap = 0;
+  // denoise.hip scratch: colour A, colour B (one float4 per pixel each), guides (two float4 per pixel)
+  float4* dn_mem = nullptr;
+  size_t dn_cap = 0;  // pixels
 };
 
 // errors without a context (api.hip); not exported from the library

@@ -21,6 +21,9 @@ int multi_set_gather(MultiDev* m, int64_t mode, std::string& err);
 int64_t multi_gather(const MultiDev* m);
 const char* multi_transport(const MultiDev* m);
 
+// ---- denoise.hip ----
+const char* denoise_params_error(const mrt_denoise_params& p);  // why mrt_denoise* rejects p, or null
+
 // ---- api.hip ----
 mrt_ctx* ctx_wrap_multi(MultiDev* m);  // the public handle of a multi-device context
 MultiDev* ctx_multi(const mrt_ctx* c);  // null for a single-device context

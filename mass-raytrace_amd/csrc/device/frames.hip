@@ -14,8 +14,9 @@
 //
 // This file uses only the public single-device entry points on the
 // per-device contexts (mrt_render_device, mrt_shard_pack/unpack_device,
-// mrt_prepass_device, mrt_tonemap_device); the single-device entry points
-// route a multi-device handle here (ctx.h MRT_DEV0 / MRT_EACH, frames.h).
+// mrt_prepass_device, mrt_tonemap_device, mrt_denoise_device); the
+// single-device entry points route a multi-device handle here (ctx.h
+// MRT_DEV0 / MRT_EACH, frames.h).
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -503,6 +504,8 @@ struct mrt_image {
   bool gathered = true;  // device 0's buffers hold every device's tiles
   float* aux = nullptr;  // device 0: albedo then normal (W*H*3 each), zero before a pre-pass
   uint8_t* rgb8 = nullptr;  // device 0: display bytes
+  mrt_denoise_params dn{};   // the Denoise view's filter (mrt_image_set_denoise)
+  float* dn_rgb = nullptr;   // device 0: the filtered colour (W*H*3)
 };
 
 extern "C" {
@@ -597,6 +600,7 @@ int mrt_image_create(mrt_ctx* ctx, uint32_t W, uint32_t H, mrt_image** out) {
   *out = nullptr;
   auto img = std::make_unique<mrt_image>();
   img->ctx = ctx;
+  mrt_denoise_default_params(&img->dn);
   const int rc = guard(ctx, [&] {
     if (!valid_size(W, H)) throw Fail{MRT_ERR_INVALID, "bad image size"};
     img->f.setup(ctx_multi(ctx), devices_of(ctx), W, H, 0, 1);
@@ -617,6 +621,7 @@ int mrt_image_destroy(mrt_image* img) {
     if (img->f.d[0].st) hipStreamSynchronize(img->f.d[0].st);
     hipFree(img->aux);
     hipFree(img->rgb8);
+    hipFree(img->dn_rgb);
   }
   ctx_images(img->ctx, -1);
   delete img;
@@ -698,7 +703,7 @@ int mrt_image_tonemap(mrt_image* img, uint32_t mode, uint8_t* out) {
   if (!img) return MRT_ERR_INVALID;
   return guard(img->ctx, [&] {
     if (!out) throw Fail{MRT_ERR_INVALID, "null output"};
-    if (mode > MRT_DISPLAY_NORMAL) throw Fail{MRT_ERR_INVALID, "bad display mode"};
+    if (mode > MRT_DISPLAY_DENOISE) throw Fail{MRT_ERR_INVALID, "bad display mode"};
     const bool aux = mode == MRT_DISPLAY_ALBEDO || mode == MRT_DISPLAY_NORMAL;
     DevFrame& d0 = img->f.d[0];
     const size_t n = img->f.npix();
@@ -710,12 +715,30 @@ int mrt_image_tonemap(mrt_image* img, uint32_t mode, uint8_t* out) {
     if (!img->rgb8) HIPF(hipMalloc(&img->rgb8, n * 3));
     if (aux && !img->aux) {  // Image::to_rgb_bytes: no buffer yet -> zeros
       HIPF(hipMemsetAsync(img->rgb8, 0, n * 3, d0.st));
+    } else if (mode == MRT_DISPLAY_DENOISE) {  // main.rs:675-683: filter, then Default's bytes
+      if (!img->dn_rgb) HIPF(hipMalloc(&img->dn_rgb, n * 12));
+      const float* albedo = img->aux;  // colour-only before a pre-pass (main.rs:737-743)
+      MRTF(d0.ctx, mrt_denoise_device(d0.ctx, img->f.W, img->f.H, d0.rgb, img->passes, albedo,
+                                      albedo ? albedo + 3 * n : nullptr, &img->dn, img->dn_rgb, d0.st));
+      MRTF(d0.ctx, mrt_tonemap_device(d0.ctx, img->f.W, img->f.H, img->dn_rgb, d0.b, img->passes ? 1 : 0,
+                                      MRT_DISPLAY_DEFAULT, img->rgb8, d0.st));
     } else {
       const float* src = aux ? img->aux + (mode == MRT_DISPLAY_NORMAL ? 3 * n : 0) : d0.rgb;
       MRTF(d0.ctx, mrt_tonemap_device(d0.ctx, img->f.W, img->f.H, src, d0.b, img->passes, mode, img->rgb8, d0.st));
     }
     HIPF(hipMemcpyAsync(out, img->rgb8, n * 3, hipMemcpyDeviceToHost, d0.st));
     HIPF(hipStreamSynchronize(d0.st));
+  });
+}
+
+int mrt_image_set_denoise(mrt_image* img, const mrt_denoise_params* params) {
+  if (!img) return MRT_ERR_INVALID;
+  return guard(img->ctx, [&] {
+    mrt_denoise_params p;
+    mrt_denoise_default_params(&p);
+    if (params) p = *params;
+    if (const char* why = denoise_params_error(p)) throw Fail{MRT_ERR_INVALID, why};
+    img->dn = p;
   });
 }
 

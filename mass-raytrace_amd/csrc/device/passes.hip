@@ -4,6 +4,7 @@
 
 #include "../host/display.h"
 #include "ctx.h"
+#include "display_math.h"
 
 using namespace mrt;
 
@@ -74,11 +75,7 @@ __global__ __launch_bounds__(kBlock) void k_selftest_division(unsigned long long
 }
 
 // ---- display (main.rs:640-722, 760-767) ----------------------------------
-// Rust f32::min/max (the non-NaN operand wins) and saturating `as u8`.
-__device__ __forceinline__ float rs_min(float a, float b) { return a != a ? b : (b != b ? a : (a < b ? a : b)); }
-__device__ __forceinline__ float rs_max(float a, float b) { return a != a ? b : (b != b ? a : (a > b ? a : b)); }
-__device__ __forceinline__ uint32_t rs_u8(float v) { return !(v > 0.0f) ? 0u : (v >= 255.0f ? 255u : (uint32_t)v); }
-
+// Rust f32::min/max and saturating `as u8`: display_math.h.
 // Default-mode byte of x = sum/passes: the count of thresholds <= x for x in
 // [0, 1] (-0.0 counts as 0); NaN or negative x -> NaN.powf -> .min(1.0) = 1.0
 // -> 255; -inf.powf = +inf and x > 1 -> 255.

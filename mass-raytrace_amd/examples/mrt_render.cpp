@@ -1,7 +1,8 @@
 // mrt_render — the C++ driver in the role of the reference's render()
 // (main.rs:150-295) + export (main.rs:760-783), written against the C ABI
 // only (include/massrt.h): build a built-in Scene, pre-pass, render N
-// passes of 1 spp into the accumulation buffers, tonemap, write PNGs.
+// passes of 1 spp into the accumulation buffers, tonemap, write PNGs
+// (<out>.png, <out>_depth.png, _albedo, _normal and _denoise).
 //
 //   mrt_render <scene> <width> <height> <passes> <out.png> [asset_dir] [device]
 //
@@ -71,6 +72,22 @@ int main(int argc, char** argv) {
       const size_t dot = path.rfind('.');
       path = (dot == std::string::npos ? path : path.substr(0, dot)) + names[mode] + ".png";
     }
+    if (mrt_write_png(path.c_str(), W, H, bytes.data()) != MRT_OK) {
+      std::fprintf(stderr, "png: %s\n", mrt_builder_last_error());
+      return 1;
+    }
+  }
+  // the Denoise view (image.dump(.., DisplayMode::Denoise), main.rs:121-127, 675-683): the guided filter over
+  // the sums and the pre-pass, then Default's bytes of the filtered colour
+  {
+    std::vector<float> filtered(n * 3);
+    if (mrt_denoise(ctx, W, H, rgb.data(), passes, albedo.data(), normal.data(), nullptr, filtered.data()) != MRT_OK)
+      return fail("mrt_denoise", ctx);
+    if (mrt_tonemap(ctx, W, H, filtered.data(), bounces.data(), passes ? 1 : 0, MRT_DISPLAY_DEFAULT, bytes.data()) !=
+        MRT_OK)
+      return fail("mrt_tonemap", ctx);
+    const size_t dot = out.rfind('.');
+    const std::string path = (dot == std::string::npos ? out : out.substr(0, dot)) + "_denoise.png";
     if (mrt_write_png(path.c_str(), W, H, bytes.data()) != MRT_OK) {
       std::fprintf(stderr, "png: %s\n", mrt_builder_last_error());
       return 1;

@@ -158,6 +158,15 @@ class MrtTuning(C.Structure):
         return {f: int(getattr(self, f)) for f, _ in self._fields_}
 
 
+class MrtDenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_albedo", C.c_float),
+                ("sigma_normal", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {"iterations": int(self.iterations), "sigma_color": float(self.sigma_color),
+                "sigma_albedo": float(self.sigma_albedo), "sigma_normal": float(self.sigma_normal)}
+
+
 GATHER_AUTO, GATHER_PEER, GATHER_RCCL = 0, 1, 2
 TRAVERSAL_AUTO, TRAVERSAL_REFERENCE, TRAVERSAL_NEAR_FIRST = -1, 0, 1
 
@@ -218,6 +227,7 @@ EXPORTED_SYMBOLS = [
     "mrt_image_render", "mrt_image_prepass", "mrt_image_read", "mrt_image_tonemap", "mrt_image_gather_stats",
     "mrt_build_info", "mrt_set_option", "mrt_get_option", "mrt_get_tuning", "mrt_context_transport", "mrt_image_gather",
     "mrt_debug_rccl_library", "mrt_debug_transport", "mrt_image_device_stats",
+    "mrt_denoise_default_params", "mrt_denoise_device", "mrt_denoise", "mrt_image_set_denoise",
 ]
 
 _lib = None
@@ -311,6 +321,10 @@ def lib() -> C.CDLL:
         "mrt_image_device_stats": (C.c_int, [P, C.c_int, C.POINTER(C.c_double)]),
         "mrt_debug_transport": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_uint32]),
         "mrt_image_gather": (I, [P]),
+        "mrt_denoise_default_params": (I, [C.POINTER(MrtDenoiseParams)]),
+        "mrt_denoise_device": (I, [P, U32, U32, P, U32, P, P, C.POINTER(MrtDenoiseParams), P, P]),
+        "mrt_denoise": (I, [P, U32, U32, fp, U32, fp, fp, C.POINTER(MrtDenoiseParams), fp]),
+        "mrt_image_set_denoise": (I, [P, C.POINTER(MrtDenoiseParams)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -674,6 +688,28 @@ class Context:
         self._check(lib().mrt_prepass(self.h, width, height, seed, _fptr(a), _fptr(n)))
         return a, n
 
+    def denoise(self, width, height, rgb, passes, albedo=None, normal=None, **params) -> np.ndarray:
+        """The Denoise view's guided filter (mrt_denoise; massrt.h states it):
+        colour sums of `passes` passes, optionally the pre-pass albedo and
+        normal -> filtered colour, float32 [H*W*3]. params: iterations,
+        sigma_color, sigma_albedo, sigma_normal (denoise_defaults()). The
+        bytes: tonemap(.., passes=1, DISPLAY_DEFAULT) of the result."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32).reshape(-1)
+        a = None if albedo is None else np.ascontiguousarray(albedo, dtype=np.float32).reshape(-1)
+        n = None if normal is None else np.ascontiguousarray(normal, dtype=np.float32).reshape(-1)
+        out = np.empty(width * height * 3, dtype=np.float32)
+        p = denoise_params(**params)
+        self._check(lib().mrt_denoise(self.h, width, height, _fptr(rgb), passes, None if a is None else _fptr(a),
+                                      None if n is None else _fptr(n), C.byref(p), _fptr(out)))
+        return out
+
+    def denoise_device(self, width, height, d_rgb: int, passes: int, d_albedo: int | None, d_normal: int | None,
+                       d_out: int, stream: int | None = None, **params):
+        p = denoise_params(**params)
+        self._check(lib().mrt_denoise_device(self.h, width, height, C.c_void_p(d_rgb), passes,
+                                             C.c_void_p(d_albedo or 0), C.c_void_p(d_normal or 0), C.byref(p),
+                                             C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
     def tonemap_device(self, width, height, d_rgb: int, d_bounces: int, passes: int, mode: int, d_out: int,
                        stream: int | None = None):
         self._check(lib().mrt_tonemap_device(self.h, width, height, C.c_void_p(d_rgb), C.c_void_p(d_bounces), passes,
@@ -721,6 +757,26 @@ def shard_pixels(width: int, height: int, shard_index: int, shard_count: int) ->
 
 
 DISPLAY_DEFAULT, DISPLAY_DEPTH, DISPLAY_ALBEDO, DISPLAY_NORMAL = 0, 1, 2, 3
+DISPLAY_DENOISE = 4  # Image.tonemap only: Context.tonemap has no albedo/normal inputs (Context.denoise, then DEFAULT)
+
+
+def denoise_defaults() -> dict:
+    """mrt_denoise_default_params: iterations, sigma_color, sigma_albedo, sigma_normal."""
+    p = MrtDenoiseParams()
+    if lib().mrt_denoise_default_params(C.byref(p)) != 0:
+        raise MassrtError(lib().mrt_global_last_error().decode())
+    return p.as_dict()
+
+
+def denoise_params(**params) -> MrtDenoiseParams:
+    """The defaults with `params` over them; an unknown name raises TypeError."""
+    d = denoise_defaults()
+    unknown = sorted(set(params) - set(d))
+    if unknown:
+        raise TypeError(f"unknown denoise parameter(s) {unknown}; there are {sorted(d)}")
+    d.update(params)
+    return MrtDenoiseParams(int(d["iterations"]), float(d["sigma_color"]), float(d["sigma_albedo"]),
+                            float(d["sigma_normal"]))
 
 
 def gamma_thresholds() -> np.ndarray:
@@ -826,8 +882,14 @@ class Image:
         (on the device, no host copy); returns once every device's work has ended."""
         self._check(lib().mrt_image_gather(self.h))
 
+    def set_denoise(self, **params):
+        """The filter of tonemap(DISPLAY_DENOISE): the defaults with `params` over them."""
+        p = denoise_params(**params)
+        self._check(lib().mrt_image_set_denoise(self.h, C.byref(p)))
+
     def tonemap(self, mode: int = 0) -> np.ndarray:
-        """Image::to_rgb_bytes + dump's row flip: (H, W, 3) uint8, top row first."""
+        """Image::to_rgb_bytes + dump's row flip: (H, W, 3) uint8, top row first.
+        DISPLAY_DENOISE filters with the image's pre-pass (colour-only before one)."""
         out = np.empty(self.width * self.height * 3, dtype=np.uint8)
         self._check(lib().mrt_image_tonemap(self.h, mode, out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out.reshape(self.height, self.width, 3)
