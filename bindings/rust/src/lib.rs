@@ -44,6 +44,8 @@ pub struct SceneSink {
     pub surfaces: Vec<mrt_surface>,
     pub textures: Vec<mrt_texture>,
     pub volumes: Vec<mrt_volume>,
+    /// EveMaterial records: an MRT_MAT_EVE material's `surface` indexes this table
+    pub eve_materials: Vec<mrt_eve_material>,
     /// RGBA8 storage the `textures` entries point into (kept alive by the sink)
     pub texels: Vec<Vec<u8>>,
     /// shared BLAS (Arc<BvhNode>) exported once, keyed by Arc::as_ptr
@@ -74,6 +76,11 @@ impl SceneSink {
         self.textures.push(mrt_texture { width, height, wrap, rgba: rgba.as_ptr() });
         self.texels.push(rgba); // the Vec's heap buffer does not move
         (self.textures.len() - 1) as u32
+    }
+
+    /// The tables beside the description (mrt_upload_scene_ext); borrows the sink.
+    pub fn desc_ext(&self) -> mrt_scene_ext {
+        mrt_scene_ext { eve_materials: self.eve_materials.as_ptr(), n_eve_materials: self.eve_materials.len() as u32 }
     }
 
     /// The boundary description; borrows the sink (valid while it lives).
@@ -152,6 +159,13 @@ impl Context {
 
     pub fn upload(&mut self, scene: &mrt_scene_desc, camera: &mrt_camera) -> Result<(), MrtError> {
         self.check(unsafe { mrt_upload_scene(self.raw, scene) })?;
+        self.check(unsafe { mrt_set_camera(self.raw, camera) })
+    }
+
+    /// `upload` for a world that holds EveMaterials (SceneSink::desc_ext).
+    pub fn upload_ext(&mut self, scene: &mrt_scene_desc, ext: &mrt_scene_ext, camera: &mrt_camera)
+        -> Result<(), MrtError> {
+        self.check(unsafe { mrt_upload_scene_ext(self.raw, scene, ext) })?;
         self.check(unsafe { mrt_set_camera(self.raw, camera) })
     }
 

@@ -39,6 +39,7 @@ pub const MRT_MAT_DIFFUSE_LIGHT: u32 = 4;
 pub const MRT_MAT_SPECULAR: u32 = 5;
 pub const MRT_MAT_ISOTROPHIC: u32 = 6;
 pub const MRT_MAT_MIX: u32 = 7;
+pub const MRT_MAT_EVE: u32 = 8;
 
 pub const MRT_SURF_SOLID: u32 = 0;
 pub const MRT_SURF_TEXTURE: u32 = 1;
@@ -212,6 +213,25 @@ pub struct mrt_scene_desc {
     pub n_volumes: u32,
 }
 
+/// EveMaterial (eve.rs:31-134): texture indices, EveMaterialColor::colors, glow.
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct mrt_eve_material {
+    pub normal_occlusion: u32,
+    pub albedo_roughness: u32,
+    pub pmdg: u32,
+    pub colors: [f32; 12],
+    pub glow: [f32; 3],
+}
+
+/// The tables beside mrt_scene_desc (mrt_upload_scene_ext).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct mrt_scene_ext {
+    pub eve_materials: *const mrt_eve_material,
+    pub n_eve_materials: u32,
+}
+
 /// Camera fields precomputed by Camera::new (world.rs:5-51).
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
@@ -246,6 +266,27 @@ pub struct mrt_hit {
     pub container: u32,
     pub t: f32,
     pub front_face: u32,
+}
+
+pub const MRT_SHADE_FRONT_FACE: u32 = 1;
+pub const MRT_SHADE_HAS_UV: u32 = 2;
+pub const MRT_SHADE_SCATTERED: u32 = 4;
+
+/// One ray shaded one step (mrt_shade_rays).
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct mrt_shade_out {
+    pub prim: u32,
+    pub container: u32,
+    pub t: f32,
+    pub flags: u32,
+    pub point: [f32; 3],
+    pub normal: [f32; 3],
+    pub uv: [f32; 2],
+    pub material: u32,
+    pub emitted: [f32; 3],
+    pub attenuation: [f32; 3],
+    pub direction: [f32; 3],
 }
 
 #[repr(C)]
@@ -341,7 +382,10 @@ extern "C" {
     pub fn mrt_global_last_error() -> *const c_char;
     pub fn mrt_abi_version() -> i32;
     pub fn mrt_upload_scene(ctx: *mut mrt_ctx, scene: *const mrt_scene_desc) -> i32;
+    pub fn mrt_upload_scene_ext(ctx: *mut mrt_ctx, scene: *const mrt_scene_desc, ext: *const mrt_scene_ext) -> i32;
     pub fn mrt_set_camera(ctx: *mut mrt_ctx, camera: *const mrt_camera) -> i32;
+    pub fn mrt_shade_rays(ctx: *mut mrt_ctx, rays: *const f32, n: u32, t_min: f32, t_max: f32, seed: u64,
+                          out: *mut mrt_shade_out) -> i32;
     pub fn mrt_render(ctx: *mut mrt_ctx, args: *const mrt_render_args, accum_rgb: *mut f32, accum_bounces: *mut u32)
         -> i32;
     pub fn mrt_render_device(ctx: *mut mrt_ctx, args: *const mrt_render_args, d_accum_rgb: *mut f32,
@@ -409,6 +453,9 @@ extern "C" {
     pub fn mrt_builder_add_volume(b: *mut mrt_builder, center: *const f32, radius: f32, density: f32,
                                   albedo: *const f32) -> i32;
     pub fn mrt_builder_mix(b: *mut mrt_builder, ratio: f32, left: u32, right: u32) -> i32;
+    pub fn mrt_builder_eve_material(b: *mut mrt_builder, no_surface: u32, ar_surface: u32, pmdg_surface: u32,
+                                    colors: *const f32, glow: *const f32) -> i32;
+    pub fn mrt_builder_desc_ext(b: *mut mrt_builder, ext: *mut mrt_scene_ext) -> i32;
     pub fn mrt_builder_background(b: *mut mrt_builder, kind: u32, surface: u32, r: f32, g: f32, bl: f32) -> i32;
     pub fn mrt_builder_background_cubemap(b: *mut mrt_builder, faces: *const u32, rotation: *const f32) -> i32;
     pub fn mrt_builder_ycbcr(b: *mut mrt_builder, luma: u32, chroma: u32) -> i32;
@@ -456,4 +503,6 @@ extern "C" {
     pub fn mrt_load_ply(path: *const c_char, out: *mut f32, cap: u64) -> i64;
     pub fn mrt_load_stl(path: *const c_char, out: *mut f32, cap: u64) -> i64;
     pub fn mrt_load_obj(path: *const c_char, out: *mut f32, cap: u64) -> i64;
+    pub fn mrt_load_obj_groups(path: *const c_char, groups: *mut *const c_char, n_groups: u32, out: *mut f32,
+                               cap: u64) -> i64;
 }

@@ -111,6 +111,8 @@ typedef struct {
 #define MRT_MAT_SPECULAR 5u      /* material.rs:331-378 (param = refraction index; surface of the inner Lambertian) */
 #define MRT_MAT_ISOTROPHIC 6u    /* material.rs:428-445 (emit[] holds the albedo) */
 #define MRT_MAT_MIX 7u           /* material.rs:391-426 (param = ratio; left, right = material indices < own) */
+#define MRT_MAT_EVE 8u           /* EveMaterial eve.rs:31-134 (surface = index into mrt_scene_ext.eve_materials;
+                                    param, emit, left, right unused; scenes uploaded with mrt_upload_scene_ext) */
 typedef struct {
   uint32_t kind;
   uint32_t surface; /* index into surfaces (Lambertian/Metal/Specular) */
@@ -196,6 +198,25 @@ typedef struct {
   uint32_t n_volumes;
 } mrt_scene_desc;
 
+/* EveMaterial (eve.rs:31-134): three Repeat textures and a palette. Per hit
+ * with uvs, scatter is Mix((roughness + dirt).min(1), Lambertian(color),
+ * Specular(1.8, color)) with color built from the texels (eve.rs:98-111) and
+ * emit is glow * pmdg(uv).w * 10; a hit without uvs neither scatters nor emits.
+ * A uv triangle whose OWN material is an EveMaterial takes its shading normal
+ * from the normal map: tangent*n.x + bitangent*n.y + normal*n.z
+ * (Material::normal, geom.rs:551-560), whatever material an instance or model
+ * override puts on the hit afterwards. */
+typedef struct {
+  uint32_t normal_occlusion, albedo_roughness, pmdg; /* texture indices (Texture::load_png, eve.rs:50-52) */
+  float colors[12];                                  /* EveMaterialColor::colors[4] */
+  float glow[3];
+} mrt_eve_material;
+/* What mrt_scene_desc has no room for (its layout is fixed): passed beside it. */
+typedef struct {
+  const mrt_eve_material* eve_materials;
+  uint32_t n_eve_materials;
+} mrt_scene_ext;
+
 /* Camera fields precomputed by Camera::new (world.rs:5-51). */
 typedef struct {
   float origin[3];
@@ -236,6 +257,21 @@ typedef struct {
   float t;
   uint32_t front_face;
 } mrt_hit;
+
+/* One ray shaded one step (Hit, Hit::emit, Hit::scatter; geom.rs:7-32): the
+ * closest hit as the winning intersect left it, then what the material emits
+ * and where it scatters. */
+#define MRT_SHADE_FRONT_FACE 1u
+#define MRT_SHADE_HAS_UV 2u
+#define MRT_SHADE_SCATTERED 4u
+typedef struct {
+  uint32_t prim, container;
+  float t;
+  uint32_t flags; /* MRT_SHADE_* */
+  float point[3], normal[3], uv[2];
+  uint32_t material; /* Hit::material after instance/model overrides */
+  float emitted[3], attenuation[3], direction[3]; /* zeros where there is none */
+} mrt_shade_out;
 
 /* Algorithmic work counters (SURVEY §8d bytes model). */
 typedef struct {
@@ -291,6 +327,10 @@ const char* mrt_global_last_error(void);
 int mrt_abi_version(void);
 
 int mrt_upload_scene(mrt_ctx* ctx, const mrt_scene_desc* scene);
+/* mrt_upload_scene with the tables mrt_scene_desc cannot carry (ext may be
+ * NULL: exactly mrt_upload_scene). An MRT_MAT_EVE material whose index is not
+ * in ext->eve_materials is MRT_ERR_INVALID. */
+int mrt_upload_scene_ext(mrt_ctx* ctx, const mrt_scene_desc* scene, const mrt_scene_ext* ext);
 int mrt_set_camera(mrt_ctx* ctx, const mrt_camera* camera);
 /* host buffers: accum_rgb = width*height*3 floats, accum_bounces = width*height */
 int mrt_render(mrt_ctx* ctx, const mrt_render_args* args, float* accum_rgb, uint32_t* accum_bounces);
@@ -302,6 +342,12 @@ int mrt_render_device(mrt_ctx* ctx, const mrt_render_args* args, float* d_accum_
  * traversal (Volume, Mix alpha tests) use ray i's stream keyed
  * (seed 0, i, sample 0xFFFFFFFE). */
 int mrt_trace_rays(mrt_ctx* ctx, const float* rays, uint32_t n, float t_min, float t_max, mrt_hit* out);
+/* The shading probe, mrt_trace_rays one step later: rays as there, out: n
+ * records. Ray i draws from one stream keyed (seed, i, sample 0xFFFFFFFD):
+ * the traversal's draws, then emit's, then scatter's, in the reference's
+ * order (world.rs:66-70). A miss gives prim = NONE and zeros. */
+int mrt_shade_rays(mrt_ctx* ctx, const float* rays, uint32_t n, float t_min, float t_max, uint64_t seed,
+                   mrt_shade_out* out);
 int mrt_get_counters(mrt_ctx* ctx, mrt_counters* out);
 int mrt_reset_counters(mrt_ctx* ctx);
 int mrt_get_kernel_stats(mrt_ctx* ctx, mrt_kernel_stats* out);
@@ -524,8 +570,8 @@ int mrt_builder_free(mrt_builder* b);
 const char* mrt_builder_last_error(void);
 /* Scene::generate of a built-in scene, then World::build_bvh (main.rs:107-112).
  * names: "sphere_grid", "cornell", "cube_field", "mesh_ply", "mesh_obj",
- *        "mesh_obj_textured", "menger", "menger_l3"; asset_dir holds cube.ply
- *        and generated assets. */
+ *        "mesh_obj_textured", "menger", "menger_l3", "eve"; asset_dir holds
+ *        cube.ply and generated assets. */
 int mrt_builder_builtin(mrt_builder* b, const char* name, float aspect_ratio, const char* asset_dir);
 float mrt_builder_rand_f32(mrt_builder* b); /* f32::rand() on the scene stream */
 /* surfaces / materials; each returns an index >= 0 */
@@ -536,6 +582,11 @@ int mrt_builder_material(mrt_builder* b, uint32_t kind, uint32_t surface, float 
 /* World::add(Volume::new(Sphere::new((), center, radius), density, albedo));
  * returns the volume index */
 int mrt_builder_add_volume(mrt_builder* b, const float* center, float radius, float density, const float* albedo);
+/* EveMaterial::new(no, ar, pmdg, colors) (eve.rs:44-64): three surfaces of kind
+ * MRT_SURF_TEXTURE (else -MRT_ERR_INVALID), colors = EveMaterialColor::colors
+ * (12 floats), glow (3 floats); returns the material index */
+int mrt_builder_eve_material(mrt_builder* b, uint32_t no_surface, uint32_t ar_surface, uint32_t pmdg_surface,
+                             const float* colors, const float* glow);
 /* Mix::new(ratio, left, right): returns the material index */
 int mrt_builder_mix(mrt_builder* b, float ratio, uint32_t left, uint32_t right);
 int mrt_builder_background(mrt_builder* b, uint32_t kind, uint32_t surface, float r, float g, float bl);
@@ -578,6 +629,8 @@ int mrt_builder_builtin_device(mrt_builder* b, const char* name, float aspect_ra
 int mrt_builder_last_build_ms(mrt_builder* b, double* host_ms, double* device_ms);
 /* flatten; pointers stay valid until the builder is freed or modified */
 int mrt_builder_desc(mrt_builder* b, mrt_scene_desc* desc, mrt_camera* camera);
+/* the tables beside the description (mrt_upload_scene_ext); pointers valid as for mrt_builder_desc */
+int mrt_builder_desc_ext(mrt_builder* b, mrt_scene_ext* ext);
 
 /* ---- display / export (main.rs:640-722, 760-783) ----------------------- */
 /* Image::to_rgb_bytes + dump's row flip: accumulated colour sums (W*H*3
@@ -672,6 +725,14 @@ int64_t mrt_load_ply(const char* path, float* out, uint64_t cap);
 int64_t mrt_load_stl(const char* path, float* out, uint64_t cap);
 /* OBJ with v/vt/vn: 24 floats per tri {v(3),n(3),uv(2)} x3, uv as read (obj_fns) */
 int64_t mrt_load_obj(const char* path, float* out, uint64_t cap);
+/* ObjLoader::load(.., obj_fns(..).with_filter(f)) (obj_loader.rs:348,394-397,431-436)
+ * with f = "the group is one of `groups`": as mrt_load_obj, keeping only the
+ * faces read while the current group is listed. `o` and `g` lines with a name
+ * set the group (a line without a name changes nothing); faces before the
+ * first such line are dropped; v/vt/vn of dropped groups still count for
+ * indexing. n_groups == 0: no filter, everything is kept. */
+int64_t mrt_load_obj_groups(const char* path, const char* const* groups, uint32_t n_groups, float* out,
+                            uint64_t cap);
 
 #ifdef __cplusplus
 }

@@ -167,8 +167,10 @@ int mrt_destroy(mrt_ctx* c) {
   return MRT_OK;
 }
 
-int mrt_upload_scene(mrt_ctx* c, const mrt_scene_desc* d) {
-  MRT_EACH(c, mrt_upload_scene(c, d));
+int mrt_upload_scene(mrt_ctx* c, const mrt_scene_desc* d) { return mrt_upload_scene_ext(c, d, nullptr); }
+
+int mrt_upload_scene_ext(mrt_ctx* c, const mrt_scene_desc* d, const mrt_scene_ext* ext) {
+  MRT_EACH(c, mrt_upload_scene_ext(c, d, ext));
   return guarded(c, [&] {
     if (!d) throw ApiError{MRT_ERR_INVALID, "null scene"};
     HostScene hs;
@@ -176,7 +178,7 @@ int mrt_upload_scene(mrt_ctx* c, const mrt_scene_desc* d) {
     // NF trees per the option in effect at upload (upload.h nf_build)
     hs.nf_build = c->opt[OPT_TRAVERSAL] == MRT_TRAVERSAL_REFERENCE ? kNfBuildNever
                   : c->opt[OPT_TRAVERSAL] == MRT_TRAVERSAL_NEAR_FIRST ? kNfBuildAlways : kNfBuildAuto;
-    if (!build_host_scene(*d, hs, err)) throw ApiError{MRT_ERR_INVALID, err};
+    if (!build_host_scene(*d, hs, err, true, ext)) throw ApiError{MRT_ERR_INVALID, err};
     build_treelet(hs, (uint32_t)((size_t)c->tun.treelet_kb * 1024 / 16));
     // one allocation, 256-B aligned sections
     size_t off = 0;
@@ -198,6 +200,7 @@ int mrt_upload_scene(mrt_ctx* c, const mrt_scene_desc* d) {
     const size_t o_bgf = sec(hs.bg_faces.size() * sizeof(GpuSurfRef));
     const size_t o_bgm = sec(sizeof(hs.bg_m));
     const size_t o_vnf = sec(hs.vnf_leaf.size() * 4);
+    const size_t o_eve = sec(hs.eve.size() * 4), o_tb = sec(hs.tri_tb.size() * 4);
     if (c->scene_mem) HIP_CHECK(hipFree(c->scene_mem));
     c->scene_mem = nullptr;
     c->has_scene = false;
@@ -226,6 +229,8 @@ int mrt_upload_scene(mrt_ctx* c, const mrt_scene_desc* d) {
     up(o_bgf, hs.bg_faces.data(), hs.bg_faces.size() * sizeof(GpuSurfRef));
     up(o_bgm, hs.bg_m, sizeof(hs.bg_m));
     up(o_vnf, hs.vnf_leaf.data(), hs.vnf_leaf.size() * 4);
+    up(o_eve, hs.eve.data(), hs.eve.size() * 4);
+    up(o_tb, hs.tri_tb.data(), hs.tri_tb.size() * 4);
     DevScene S = host_dev_scene(hs);  // sizes and flags; its pointers now go to the device copies
     S.slots = (const uint32_t*)(base + o_slots);
     S.slots_tl = (const uint32_t*)(base + o_stl);
@@ -250,6 +255,8 @@ int mrt_upload_scene(mrt_ctx* c, const mrt_scene_desc* d) {
     S.bg_faces = (const GpuSurfRef*)(base + o_bgf);
     S.bg_m = (const float*)(base + o_bgm);
     S.vnf_leaf = (const uint32_t*)(base + o_vnf);
+    S.eve = (const float*)(base + o_eve);
+    S.tri_tb = hs.tri_tb.empty() ? nullptr : (const float*)(base + o_tb);
     c->S = S;
     c->scene_bytes = off;
     // the reference stream's size decides the per-scene rules (the NF trees follow it)
@@ -259,7 +266,7 @@ int mrt_upload_scene(mrt_ctx* c, const mrt_scene_desc* d) {
     c->facts.treelet = S.n_tlet > 0;
     c->facts.trav_rng = hs.trav_rng;
     c->scene_alpha = hs.has_alpha;
-    c->scene_ext = !hs.surf_ops.empty() || hs.bg_kind == MRT_BG_CUBEMAP;
+    c->scene_ext = !hs.surf_ops.empty() || hs.bg_kind == MRT_BG_CUBEMAP || !hs.eve.empty();
     apply_options(c);  // the per-scene rules of the options left at -1
     c->has_scene = true;
   });

@@ -164,6 +164,7 @@ struct TriShade {
   V3 a, b, c, na, nb, nc;
   V2 uva, uvb, uvc;
   uint32_t material, flags;
+  uint32_t eve;  // TRI_FLAG_EVE: the Eve record of the triangle's own material
 };
 MRT_HD TriShade load_tri(const DevScene& S, uint32_t id) {
   const float4* q = reinterpret_cast<const float4*>(S.tri_shade) + (size_t)MRT_IDX(S, id, S.n_tris, 3) * kTriShadeQuads;
@@ -180,6 +181,7 @@ MRT_HD TriShade load_tri(const DevScene& S, uint32_t id) {
   s.uvc = V2{q5.z, q5.w};
   s.material = f2u(q6.x);
   s.flags = f2u(q6.y);
+  s.eve = f2u(q6.z);
   return s;
 }
 

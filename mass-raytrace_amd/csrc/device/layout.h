@@ -49,7 +49,9 @@ constexpr uint32_t kLdsTag = 0x40000000u;
 constexpr uint32_t kIdxMask = 0x3FFFFFFFu;
 // the region being traversed has ended (record after its last one; walk.h)
 constexpr uint32_t KIND_END = 0;
-enum : uint32_t { TRI_FLAG_ALPHA = 1u, TRI_FLAG_UV = 2u };  // tri_shade flags
+// tri_shade flags; TRI_FLAG_EVE: the triangle's own material is an EveMaterial
+// at its root (its shading normal comes from that material's normal map)
+enum : uint32_t { TRI_FLAG_ALPHA = 1u, TRI_FLAG_UV = 2u, TRI_FLAG_EVE = 4u };
 // a TRI record's slot1.z: the triangle id, bit 31 = the triangle is alpha-tested
 constexpr uint32_t kTriAlpha = 0x80000000u;
 constexpr uint32_t kTriIdMask = 0x0FFFFFFFu;
@@ -153,8 +155,14 @@ MRT_HD uint32_t texel_index(uint32_t tpr, uint32_t x, uint32_t y) {
 // Per-triangle shading record, 7 x float4 (112 B):
 //  0 {a.x a.y a.z b.x} 1 {b.y b.z c.x c.y} 2 {c.z na.x na.y na.z}
 //  3 {nb.x nb.y nb.z nc.x} 4 {nc.y nc.z uva.x uva.y} 5 {uvb.x uvb.y uvc.x uvc.y}
-//  6 {material, flags, 0, 0}
+//  6 {material, flags, eve record (TRI_FLAG_EVE), 0}
 constexpr uint32_t kTriShadeQuads = 7;
+
+// EveMaterial record (eve.rs:31-36,136-139), 5 x 16 B; GpuMaterial.texture of
+// an MRT_MAT_EVE material names it:
+//  0 {normal_occlusion, albedo_roughness, pmdg (texture indices), 0}
+//  1-3 colors[4] as 12 floats   4 {glow.x glow.y glow.z 0}
+constexpr uint32_t kEveQuads = 5;
 
 // Kernel-visible scene (plain pointers into one device allocation).
 struct DevScene {
@@ -196,6 +204,10 @@ struct DevScene {
   uint32_t vnf_base[4];        // first vnf_leaf entry of spheres, triangles, instances, models
   uint32_t n_vnf;
   NfBound nfb;                 // the walk's rounding margins (nf_bound.h)
+  // EveMaterial (read by the EXT kernel variants only)
+  const float* eve;            // kEveQuads*4 words per record
+  const float* tri_tb;         // {T.xyz 0}{B.xyz 0} per triangle; null unless the scene has an Eve material
+  uint32_t n_eve;
 };
 
 }  // namespace mrt

@@ -27,7 +27,29 @@ struct Surf {
 #define MRT_PIN_LOAD(x) (void)0
 #endif
 
-MRT_HD Surf resolve_hit(const DevScene& S, V3 o, V3 d, const Hit& h) {
+// An EveMaterial record (layout.h kEveQuads): its texture indices.
+struct EveTex {
+  uint32_t normal_occlusion, albedo_roughness, pmdg;
+};
+MRT_HD const float* eve_record(const DevScene& S, uint32_t rec) {
+  return S.eve + (size_t)MRT_IDX(S, rec, S.n_eve, 25) * (kEveQuads * 4);
+}
+MRT_HD EveTex load_eve_tex(const DevScene& S, uint32_t rec) {
+  const float4 q = *reinterpret_cast<const float4*>(eve_record(S, rec));
+  return EveTex{f2u(q.x), f2u(q.y), f2u(q.z)};
+}
+// EveMaterial::normal_occlusion (eve.rs:66-73): the tangent-space normal
+MRT_HD V3 eve_tangent_normal(const DevScene& S, uint32_t rec, V2 uv, LocalCounters& lc) {
+  const V4 px = texture_get_f(S, load_eve_tex(S, rec).normal_occlusion, uv, lc);
+  const float py = px.y * 2.0f - 1.0f, pw = px.w * 2.0f - 1.0f;
+  const float x = (1.0f - py * py) - pw * pw;
+  return unit(V3{py, pw, sqrtf(fabsf(x))});
+}
+
+// EXT: the scene may hold EveMaterial triangles, whose normal is mapped
+// (Material::normal, geom.rs:551-560); lc counts the normal map's taps.
+template <bool EXT>
+MRT_HD Surf resolve_hit(const DevScene& S, V3 o, V3 d, const Hit& h, LocalCounters& lc) {
   Surf s;
   V3 ro = o, rd = d;
   const uint32_t ckind = h.container >> 28, cidx = h.container & 0x0FFFFFFFu;
@@ -68,12 +90,24 @@ MRT_HD Surf resolve_hit(const DevScene& S, V3 o, V3 d, const Hit& h) {
     s.uv = V2{0, 0};
   } else {
     TriShade t = load_tri(S, pidx);
+    // the tangent frame with the triangle's other quads (a scene without an
+    // Eve material has none: a uniform branch)
+    float4 tq{}, bq{};
+    if (EXT && S.tri_tb) {
+      const float4* tb = reinterpret_cast<const float4*>(S.tri_tb) + (size_t)MRT_IDX(S, pidx, S.n_tris, 3) * 2;
+      tq = tb[0], bq = tb[1];
+    }
     float a0, a1, a2;
     tri_bary(t, s.point, a0, a1, a2);
     outward = (t.na * a0 + t.nb * a1) + t.nc * a2;
     s.has_uv = (t.flags & TRI_FLAG_UV) != 0;
     s.uv = uv_or_zero(s.has_uv, (t.uva * a0 + t.uvb * a1) + t.uvc * a2);
     s.material = t.material;
+    // the triangle's OWN material's normal map (geom.rs:554), whatever override follows
+    if (EXT && S.tri_tb && s.has_uv && (t.flags & TRI_FLAG_EVE)) {
+      const V3 tn = eve_tangent_normal(S, t.eve, s.uv, lc);
+      outward = ((V3{tq.x, tq.y, tq.z} * tn.x) + (V3{bq.x, bq.y, bq.z} * tn.y)) + (outward * tn.z);
+    }
   }
   // Hit::set_face_normal in the intersecting (object) space (geom.rs:17-24)
   s.front_face = dot(rd, outward) < 0.0f;
@@ -85,6 +119,11 @@ MRT_HD Surf resolve_hit(const DevScene& S, V3 o, V3 d, const Hit& h) {
   }
   if (over != MRT_NO_MATERIAL) s.material = over;
   return s;
+}
+// scenes without an Eve material (the non-EXT kernels, the host checks)
+MRT_HD Surf resolve_hit(const DevScene& S, V3 o, V3 d, const Hit& h) {
+  LocalCounters lc;
+  return resolve_hit<false>(S, o, d, h, lc);
 }
 
 // ---- sampling (math.rs:262-291) -----------------------------------------------
@@ -236,14 +275,48 @@ MRT_DEV bool scatter(const DevScene& S, const Surf& s, V3 d, PathRng& rng, V3& e
   const MatHead root = load_mat_head(S, s.material);
   root_kind = root.kind;
   emitted = V3{0, 0, 0};
+  // EveMaterial: the paint/material/dirt/glow texel of the record emit picked,
+  // kept for scatter (the same record unless a Mix picked another)
+  uint32_t pmdg_rec = 0xFFFFFFFFu;
+  V4 pmdg{};
   {
     MatHead e = root;
     mix_pick(S, s.material, e, rng);
     if (e.kind == MRT_MAT_DIFFUSE_LIGHT) emitted = V3{e.color[0], e.color[1], e.color[2]};
+    if (EXT && e.kind == MRT_MAT_EVE && s.has_uv) {  // eve.rs:121-128
+      pmdg_rec = e.texture;
+      pmdg = texture_get_f(S, load_eve_tex(S, pmdg_rec).pmdg, s.uv, lc);
+      const float* g = eve_record(S, pmdg_rec) + 16;
+      emitted = (V3{g[0], g[1], g[2]} * pmdg.w) * 10.0f;
+    }
   }
   MatHead m = root;
   const uint32_t mi = mix_pick(S, s.material, m, rng);
   V2 uv = uv_or_zero(s.has_uv, s.uv);
+  if (EXT && m.kind == MRT_MAT_EVE) {  // EveMaterial::scatter (eve.rs:92-119)
+    if (!s.has_uv) return false;
+    const uint32_t rec = m.texture;
+    const EveTex tex = load_eve_tex(S, rec);
+    const V4 ar = texture_get_f(S, tex.albedo_roughness, s.uv, lc);
+    if (rec != pmdg_rec) pmdg = texture_get_f(S, tex.pmdg, s.uv, lc);
+    const V3 albedo{ar.x, ar.y, ar.z};
+    const float roughness = ar.w, paint = pmdg.x, dirt = pmdg.z;
+    // EveMaterialColor::get (eve.rs:190-198); the reference would panic past colors[3]
+    const float i = pmdg.y * 3.0f;
+    uint32_t i0 = f2usize(floorf(i)), i1 = f2usize(ceilf(i));
+    i0 = i0 < 3u ? i0 : 3u;
+    i1 = i1 < 3u ? i1 : 3u;
+    const float t = i - (float)i0;
+    const float* pal = eve_record(S, rec) + 4;
+    const V3 mc = (ld3(pal + 3 * i0) * (1.0f - t)) + (ld3(pal + 3 * i1) * t);
+    const V3 color = ((((albedo * mc) * (1.0f - paint)) + (albedo * paint)) * (1.0f - fminf(dirt, 1.0f))) +
+                     (V3{0.01f, 0.005f, 0.0f} * dirt);
+    // Mix::new(ratio, Lambertian::new(color), Specular::new(1.8, color)).scatter: one draw
+    // picks the side, which then runs below as any Lambertian or Specular over a SolidColor
+    const float ratio = fminf(roughness + dirt, 1.0f);
+    m = MatHead{rng.f32() < ratio ? MRT_MAT_LAMBERTIAN : MRT_MAT_SPECULAR, MRT_SURF_SOLID, 0u, 1.8f,
+                {color.x, color.y, color.z, 1.0f}};
+  }
   switch (m.kind) {
     case MRT_MAT_LAMBERTIAN:
       lambertian<EXT>(S, m, mi, s, rng, atten, new_d, lc);

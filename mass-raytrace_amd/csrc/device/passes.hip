@@ -140,7 +140,7 @@ __global__ __launch_bounds__(kBlock) void k_prepass(DevScene S, DevCamera cam, u
   const Hit h = closest_hit<false, RNG, EXT>(tin, p, INFINITY, lc, rng);
   V3 a{0.0f, 0.0f, 0.0f}, n{0.0f, 0.0f, 0.0f};
   if (h.prim != kRefNone) {
-    Surf s = resolve_hit(S, o, d, h);
+    Surf s = resolve_hit<EXT>(S, o, d, h, lc);
     V3 emitted, atten, nd;
     uint32_t mkind;
     a = scatter<EXT>(S, s, d, rng, emitted, atten, nd, lc, mkind) ? atten : emitted;
@@ -150,6 +150,44 @@ __global__ __launch_bounds__(kBlock) void k_prepass(DevScene S, DevCamera cam, u
   }
   albedo[3 * (size_t)p] = a.x, albedo[3 * (size_t)p + 1] = a.y, albedo[3 * (size_t)p + 2] = a.z;
   normal[3 * (size_t)p] = n.x, normal[3 * (size_t)p + 1] = n.y, normal[3 * (size_t)p + 2] = n.z;
+}
+
+// mrt_shade_rays: ray i traced and shaded one step (a test entry point, not
+// hot). One stream per ray: the traversal's draws, emit's, scatter's.
+template <bool RNG, bool EXT>
+__global__ __launch_bounds__(kBlock) void k_shade_rays(DevScene S, const float* rays, uint32_t n, float tmin,
+                                                       float tmax, unsigned long long seed, float4* ray_ro,
+                                                       float4* ray_rd, mrt_shade_out* out) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const float* r = rays + 6 * (size_t)i;
+  const V3 o{r[0], r[1], r[2]}, d{r[3], r[4], r[5]};
+  ray_ro[i] = make_float4(o.x, o.y, o.z, 0.0f);
+  ray_rd[i] = make_float4(d.x, d.y, d.z, 0.0f);
+  PathRng rng = path_rng(seed, i, 0xFFFFFFFDu);
+  const TravIn tin{S, reinterpret_cast<const uint4*>(S.slots), S.world_begin, ray_ro, ray_rd, tmin};
+  LocalCounters lc;
+  const Hit h = closest_hit<false, RNG, EXT>(tin, i, tmax, lc, rng);
+  mrt_shade_out w{};
+  if (h.prim != kRefNone) {
+    const Surf s = resolve_hit<EXT>(S, o, d, h, lc);
+    V3 emitted, atten{0, 0, 0}, nd{0, 0, 0};
+    uint32_t mkind;
+    const bool cont = scatter<EXT>(S, s, d, rng, emitted, atten, nd, lc, mkind);
+    w.prim = h.prim, w.container = h.container, w.t = h.t;
+    w.flags = (s.front_face ? MRT_SHADE_FRONT_FACE : 0u) | (s.has_uv ? MRT_SHADE_HAS_UV : 0u) |
+              (cont ? MRT_SHADE_SCATTERED : 0u);
+    w.point[0] = s.point.x, w.point[1] = s.point.y, w.point[2] = s.point.z;
+    w.normal[0] = s.normal.x, w.normal[1] = s.normal.y, w.normal[2] = s.normal.z;
+    w.uv[0] = s.has_uv ? s.uv.x : 0.0f, w.uv[1] = s.has_uv ? s.uv.y : 0.0f;
+    w.material = s.material;
+    w.emitted[0] = emitted.x, w.emitted[1] = emitted.y, w.emitted[2] = emitted.z;
+    if (cont) {
+      w.attenuation[0] = atten.x, w.attenuation[1] = atten.y, w.attenuation[2] = atten.z;
+      w.direction[0] = nd.x, w.direction[1] = nd.y, w.direction[2] = nd.z;
+    }
+  }
+  out[i] = w;
 }
 
 // One thread per pixel; writes the pixel's 3 bytes at the flipped row.
@@ -398,6 +436,38 @@ int mrt_prepass(mrt_ctx* c, uint32_t W, uint32_t H, uint64_t seed, float* albedo
     HIP_CHECK(hipMemcpyAsync(normal, d + 3 * n, n * 12, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipStreamSynchronize(c->stream));
     HIP_CHECK(hipFree(d));
+  });
+}
+
+int mrt_shade_rays(mrt_ctx* c, const float* rays, uint32_t n, float t_min, float t_max, uint64_t seed,
+                   mrt_shade_out* out) {
+  MRT_DEV0(c, mrt_shade_rays(c, rays, n, t_min, t_max, seed, out));
+  return guarded(c, [&] {
+    if (!c->has_scene) throw ApiError{MRT_ERR_STATE, "no scene uploaded"};
+    if (n == 0) return;
+    if (!rays || !out) throw ApiError{MRT_ERR_INVALID, "null argument"};
+    wait_queues(c, c->stream);
+    ensure_slots(c, n);  // the rays where the traversal re-reads them
+    char* mem = nullptr;
+    const size_t ray_bytes = ((size_t)n * 24 + 255) & ~(size_t)255;
+    HIP_CHECK(hipMalloc(&mem, ray_bytes + (size_t)n * sizeof(mrt_shade_out)));
+    float* d_rays = (float*)mem;
+    mrt_shade_out* d_out = (mrt_shade_out*)(mem + ray_bytes);
+    try {
+      HIP_CHECK(hipMemcpyAsync(d_rays, rays, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
+      auto* f = c->facts.trav_rng ? (c->scene_ext ? k_shade_rays<true, true> : k_shade_rays<true, false>)
+                                  : (c->scene_ext ? k_shade_rays<false, true> : k_shade_rays<false, false>);
+      hipLaunchKernelGGL(f, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->S, (const float*)d_rays, n,
+                         t_min, t_max, (unsigned long long)seed, c->slot_ro, c->slot_rd, d_out);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(mrt_shade_out), hipMemcpyDeviceToHost, c->stream));
+      HIP_CHECK(hipStreamSynchronize(c->stream));
+    } catch (...) {
+      hipFree(mem);
+      throw;
+    }
+    HIP_CHECK(hipFree(mem));
+    mark_ctx_busy(c, c->stream);  // slot_ro/slot_rd are shared with the drain hand-off
   });
 }
 

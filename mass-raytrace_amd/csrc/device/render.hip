@@ -641,12 +641,12 @@ void render_device(mrt_ctx* c, const mrt_render_args* a, float* d_rgb, uint32_t*
   // results slab <= results_max samples (16 B each); pool <= pool_paths
   uint32_t spp_chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(a->spp_count, c->tun.results_max / n_pix));
   if (simple && c->scene_ext)
-    throw ApiError{MRT_ERR_INVALID, "MRT_RENDER_SIMPLE_TRACE does not support composite surfaces or CubeMap backgrounds"};
+    throw ApiError{MRT_ERR_INVALID, "MRT_RENDER_SIMPLE_TRACE does not support composite surfaces, CubeMap backgrounds or Eve materials"};
   if ((a->flags & MRT_RENDER_FUSED) && !simple) {
     if (scene_rng)
       throw ApiError{MRT_ERR_INVALID, "MRT_RENDER_FUSED does not support scenes whose traversal draws (Volume, Mix alpha)"};
     if (c->scene_ext)
-      throw ApiError{MRT_ERR_INVALID, "MRT_RENDER_FUSED does not support composite surfaces or CubeMap backgrounds"};
+      throw ApiError{MRT_ERR_INVALID, "MRT_RENDER_FUSED does not support composite surfaces, CubeMap backgrounds or Eve materials"};
     render_fused(c, a, pl.first, n_pix, spp_chunk, d_rgb, d_b, st);
     return;
   }

@@ -24,7 +24,7 @@ MRT_DEV bool shade_step(const DevScene& S, uint32_t max_depth, const Hit& h, V3&
     L = L + T * background<EXT>(S, d, lc);
     return false;
   }
-  Surf s = resolve_hit(S, o, d, h);
+  Surf s = resolve_hit<EXT>(S, o, d, h, lc);
   mat = s.material;
   V3 emitted, atten, nd;
   bool cont = scatter<EXT>(S, s, d, rng, emitted, atten, nd, lc, mkind);

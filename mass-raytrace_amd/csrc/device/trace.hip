@@ -253,6 +253,7 @@ __global__ __launch_bounds__(kBlock) void k_rays_in(const float* rays, uint32_t 
   out.rng[i] = make_uint4((uint32_t)g.s0, (uint32_t)(g.s0 >> 32), (uint32_t)g.s1, (uint32_t)(g.s1 >> 32));
 }
 
+template <bool EXT>
 __global__ __launch_bounds__(kBlock) void k_rays_out(DevScene S, PathBufs in, const uint4* hits, uint32_t n,
                                                      uint4* out) {
   uint32_t i = blockIdx.x * kBlock + threadIdx.x;
@@ -261,8 +262,9 @@ __global__ __launch_bounds__(kBlock) void k_rays_out(DevScene S, PathBufs in, co
   const uint4 hv = hits[i];
   Hit h{__uint_as_float(hv.x), hv.y, hv.z};
   uint32_t front = 0;
+  LocalCounters lc;  // a mapped normal decides front_face (EXT): its taps are not counted
   if (h.prim != kRefNone)
-    front = resolve_hit(S, V3{o4.x, o4.y, o4.z}, V3{d4.x, d4.y, d4.z}, h).front_face ? 1u : 0u;
+    front = resolve_hit<EXT>(S, V3{o4.x, o4.y, o4.z}, V3{d4.x, d4.y, d4.z}, h, lc).front_face ? 1u : 0u;
   out[i] = make_uint4(h.prim, h.container, __float_as_uint(h.prim != kRefNone ? h.t : 0.0f), front);
 }
 
@@ -369,8 +371,8 @@ extern "C" int mrt_trace_rays(mrt_ctx* c, const float* rays, uint32_t n, float t
     Ctrl init{{n, 0}, n, 0};
     HIP_CHECK(hipMemcpyAsync(q.ctrl, &init, sizeof(Ctrl), hipMemcpyHostToDevice, c->stream));
     launch_trace(c, c->stream, q, q.bufs[0], 0u, true, t_min, t_max);
-    hipLaunchKernelGGL(k_rays_out, dim3(g), dim3(kBlock), 0, c->stream, c->S, q.bufs[0], (const uint4*)q.hits, n,
-                       c->d_rhits);
+    hipLaunchKernelGGL(c->scene_ext ? k_rays_out<true> : k_rays_out<false>, dim3(g), dim3(kBlock), 0, c->stream, c->S,
+                       q.bufs[0], (const uint4*)q.hits, n, c->d_rhits);
     HIP_CHECK(hipGetLastError());
     std::vector<uint4> h(n);
     HIP_CHECK(hipMemcpyAsync(h.data(), c->d_rhits, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));

@@ -433,7 +433,8 @@ void put_m4_12(std::vector<float>& dst, const float* m16) {
 
 }  // namespace
 
-bool build_host_scene(const mrt_scene_desc& d, HostScene& s, std::string& err, bool sibling_layout) {
+bool build_host_scene(const mrt_scene_desc& d, HostScene& s, std::string& err, bool sibling_layout,
+                      const mrt_scene_ext* ext) {
   const bool keep = s.keep_nf_boxes;
   const int nf_build = s.nf_build;
   s = HostScene{};
@@ -447,7 +448,7 @@ bool build_host_scene(const mrt_scene_desc& d, HostScene& s, std::string& err, b
     GpuMaterial g{};
     g.kind = m.kind;
     g.param = m.param;
-    if (m.kind > MRT_MAT_MIX) return (err = "bad material kind", false);
+    if (m.kind > MRT_MAT_EVE) return (err = "bad material kind", false);
     if (m.kind == MRT_MAT_LAMBERTIAN || m.kind == MRT_MAT_METAL || m.kind == MRT_MAT_SPECULAR) {
       if (m.surface >= d.n_surfaces) return (err = "material surface out of range", false);
       GpuSurfRef r;
@@ -463,8 +464,25 @@ bool build_host_scene(const mrt_scene_desc& d, HostScene& s, std::string& err, b
       if (m.left >= i || m.right >= i) return (err = "Mix children must precede the Mix in the material table", false);
       g.left = m.left;
       g.right = m.right;
+    } else if (m.kind == MRT_MAT_EVE) {
+      if (!ext || !ext->eve_materials || m.surface >= ext->n_eve_materials)
+        return (err = "eve material index out of range", false);
+      g.texture = m.surface;  // the Eve record
     }
     s.materials.push_back(g);
+  }
+  // EveMaterial records (layout.h); only the referenced table matters, but all of it is checked
+  const uint32_t n_eve = ext && ext->eve_materials ? ext->n_eve_materials : 0;
+  for (uint32_t i = 0; i < n_eve; ++i) {
+    const mrt_eve_material& e = ext->eve_materials[i];
+    if (e.normal_occlusion >= d.n_textures || e.albedo_roughness >= d.n_textures || e.pmdg >= d.n_textures)
+      return (err = "eve material texture out of range", false);
+    float q[kEveQuads * 4] = {};
+    const uint32_t tex[3] = {e.normal_occlusion, e.albedo_roughness, e.pmdg};
+    memcpy(q, tex, 12);
+    memcpy(q + 4, e.colors, 48);
+    memcpy(q + 16, e.glow, 12);
+    s.eve.insert(s.eve.end(), q, q + kEveQuads * 4);
   }
   // textures
   for (uint32_t i = 0; i < d.n_textures; ++i) {
@@ -509,9 +527,21 @@ bool build_host_scene(const mrt_scene_desc& d, HostScene& s, std::string& err, b
                    t.nb[2],  t.nc[0],  t.nc[1],  t.nc[2],  t.uva[0], t.uva[1], t.uvb[0],
                    t.uvb[1], t.uvc[0], t.uvc[1], 0,        0,        0,        0};
     uint32_t flags = (t.flags & MRT_TRI_HAS_UV) ? TRI_FLAG_UV : 0;
+    if (d.materials[t.material].kind == MRT_MAT_EVE) {  // Material::normal is Some only for EveMaterial itself
+      flags |= TRI_FLAG_EVE;
+      memcpy(&q[26], &d.materials[t.material].surface, 4);
+    }
     memcpy(&q[24], &t.material, 4);
     memcpy(&q[25], &flags, 4);
     s.tri_shade.insert(s.tri_shade.end(), q, q + 28);
+  }
+  if (!s.eve.empty()) {  // tangent frames (geom.rs:444-445), read only by triangles carrying TRI_FLAG_EVE
+    s.tri_tb.reserve((size_t)d.n_triangles * 8);
+    for (uint32_t i = 0; i < d.n_triangles; ++i) {
+      const mrt_triangle& t = d.triangles[i];
+      const float q[8] = {t.tangent[0], t.tangent[1], t.tangent[2], 0, t.bitangent[0], t.bitangent[1], t.bitangent[2], 0};
+      s.tri_tb.insert(s.tri_tb.end(), q, q + 8);
+    }
   }
   // volumes (geom.rs:602-607: neg_inv_density = -1.0 / density)
   for (uint32_t i = 0; i < d.n_volumes; ++i) {

@@ -23,6 +23,8 @@ struct HostScene {
   std::vector<float> sph;
   std::vector<uint32_t> sph_mat;
   std::vector<float> tri_shade;
+  std::vector<float> eve;     // EveMaterial records (layout.h kEveQuads)
+  std::vector<float> tri_tb;  // tangent / bitangent per triangle; empty unless the scene has an Eve material
   std::vector<GpuMaterial> materials;
   std::vector<GpuTexture> textures;
   std::vector<uint32_t> texels;
@@ -116,6 +118,9 @@ inline DevScene host_dev_scene(const HostScene& s) {
   for (int k = 0; k < 4; ++k) S.vnf_base[k] = s.vnf_base[k];
   S.n_vnf = (uint32_t)(s.vnf_leaf.size() / 2);
   S.nfb = s.nfb;
+  S.eve = s.eve.data();
+  S.tri_tb = s.tri_tb.empty() ? nullptr : s.tri_tb.data();
+  S.n_eve = (uint32_t)(s.eve.size() / (kEveQuads * 4));
   return S;
 }
 
@@ -128,7 +133,9 @@ bool build_nf_trees(const mrt_scene_desc& d, HostScene& s, std::string& err);
 // Validates the description and linearises it. Returns false with `err` set.
 // sibling_layout=false keeps every region in plain preorder (the layout
 // before round 2; tools/slab_check.cpp runs the walk over both: they walk alike)
-bool build_host_scene(const mrt_scene_desc& d, HostScene& out, std::string& err, bool sibling_layout = true);
+// ext: the tables beside the description (mrt_upload_scene_ext); null: none.
+bool build_host_scene(const mrt_scene_desc& d, HostScene& out, std::string& err, bool sibling_layout = true,
+                      const mrt_scene_ext* ext = nullptr);
 
 // Chooses the records copied into LDS by every k_trace workgroup (at most
 // `budget` 16-byte slots): the whole stream when it fits; else the small BLAS

@@ -142,6 +142,26 @@ int mrt_builder_material(mrt_builder* b, uint32_t kind, uint32_t surface, float 
   });
 }
 
+int mrt_builder_eve_material(mrt_builder* b, uint32_t no_surface, uint32_t ar_surface, uint32_t pmdg_surface,
+                             const float* colors, const float* glow) {
+  return guard(b, [&] {
+    if (!colors || !glow) throw Error(MRT_ERR_INVALID, "null argument");
+    const uint32_t idx[3] = {no_surface, ar_surface, pmdg_surface};
+    SharedTexture tex[3];
+    for (int k = 0; k < 3; ++k) {
+      if (idx[k] >= b->surfaces.size()) throw Error(MRT_ERR_INVALID, "surface index out of range");
+      if (b->surfaces[idx[k]].kind != MRT_SURF_TEXTURE)
+        throw Error(MRT_ERR_INVALID, "EveMaterial planes must be texture surfaces");
+      tex[k] = b->surfaces[idx[k]].texture;
+    }
+    EveMaterialColor c;
+    for (int k = 0; k < 4; ++k) c.colors[k] = v3p(colors + 3 * k);
+    c.glow = v3p(glow);
+    b->materials.push_back(EveMaterial(tex[0], tex[1], tex[2], c));
+    return (int)b->materials.size() - 1;
+  });
+}
+
 int mrt_builder_mix(mrt_builder* b, float ratio, uint32_t left, uint32_t right) {
   return guard(b, [&] {
     if (left >= b->materials.size() || right >= b->materials.size())
@@ -352,6 +372,16 @@ int mrt_builder_desc(mrt_builder* b, mrt_scene_desc* desc, mrt_camera* camera) {
   return rc < 0 ? -rc : rc;
 }
 
+int mrt_builder_desc_ext(mrt_builder* b, mrt_scene_ext* ext) {
+  int rc = guard(b, [&] {
+    if (!ext) throw Error(MRT_ERR_INVALID, "null output");
+    b->world->desc();  // interns what the objects reference
+    *ext = b->world->desc_ext();
+    return 0;
+  });
+  return rc < 0 ? -rc : rc;
+}
+
 static int64_t copy_tris(const std::vector<std::array<V3, 3>>& f, float* out, uint64_t cap) {
   if (out) {
     uint64_t n = std::min<uint64_t>(cap, f.size());
@@ -400,8 +430,16 @@ int64_t mrt_load_stl(const char* path, float* out, uint64_t cap) {
 }
 
 int64_t mrt_load_obj(const char* path, float* out, uint64_t cap) {
+  return mrt_load_obj_groups(path, nullptr, 0, out, cap);
+}
+
+int64_t mrt_load_obj_groups(const char* path, const char* const* groups, uint32_t n_groups, float* out,
+                            uint64_t cap) {
   try {
-    ObjResult r = load_obj(path ? path : "");
+    if (n_groups && !groups) throw Error(MRT_ERR_INVALID, "null group list");
+    std::vector<std::string> keep;
+    for (uint32_t i = 0; i < n_groups; ++i) keep.push_back(groups[i] ? groups[i] : "");
+    ObjResult r = n_groups ? load_obj(path ? path : "", &keep) : load_obj(path ? path : "");
     if (out) {
       uint64_t n = std::min<uint64_t>(cap, r.faces.size());
       for (uint64_t i = 0; i < n; ++i)

@@ -369,7 +369,7 @@ static std::string with_file_name(const std::string& path, const std::string& na
   return p == std::string::npos ? name : path.substr(0, p + 1) + name;
 }
 
-ObjResult load_obj(const std::string& path) {
+ObjResult load_obj(const std::string& path, const std::vector<std::string>* groups) {
   std::ifstream in(path);
   if (!in) throw Error(MRT_ERR_IO, "cannot open " + path);
   std::vector<V3> verts, norms;
@@ -377,6 +377,8 @@ ObjResult load_obj(const std::string& path) {
   ObjResult res;
   std::string material;
   std::string line;
+  // include_group(&context) with no group yet: a filter sees None (EveFilter: false)
+  bool include_faces = groups == nullptr;
   while (std::getline(in, line)) {
     std::vector<std::string> parts = split_ws(line);
     if (parts.empty()) continue;
@@ -391,7 +393,11 @@ ObjResult load_obj(const std::string& path) {
       if (parts.size() < 3 || !parse_f32(parts[1], u) || !parse_f32(parts[2], v))
         throw Error(MRT_ERR_IO, "unable to parse texture coord: " + line);
       uvs.push_back(V2{u, v});
+    } else if (k == "o" || k == "g") {  // a line without a name leaves the group and the decision as they are
+      if (groups && parts.size() > 1)
+        include_faces = std::find(groups->begin(), groups->end(), parts[1]) != groups->end();
     } else if (k == "f") {
+      if (!include_faces) continue;
       // obj_loader.rs:398-429: only the first three corners; `v//vn` borrows uvs[0]
       ObjFace face;
       for (int c = 0; c < 3; ++c) {

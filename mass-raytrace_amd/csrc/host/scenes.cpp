@@ -8,6 +8,8 @@
 //   menger       = Menger::generate       scenes/menger.rs:20-105 (20^5 = 3.2M cube
 //                  instances); menger_l3 = the same with the
 //                  three innermost levels only (8,000 cubes, for quick tests)
+//   eve          = Eve::generate          scenes/eve.rs:21-97 (two EveMaterial hulls —
+//                  generated stand-ins, load_ship below —, a 6x6 fleet, a Volume, the sun)
 // The scene RNG is the world's wyrand stream (fastrand::seed(1), main.rs:86);
 // draws happen in the same statement order as the Rust scenes.
 #include <stdio.h>
@@ -236,6 +238,73 @@ SceneResult menger(float aspect, const std::string& assets, uint64_t seed, int l
   return r;
 }
 
+// eve::load_ship (eve.rs:216-340): EveMaterial::new over the hull's three
+// PNGs, the hull's OBJ through obj_fns(.., with_norms_and_uvs).with_filter(EveFilter),
+// Model::new. The one substitution of this scene: the reference's hulls
+// (models/<hull>/..) are proprietary game assets that are not in the
+// reference's tree, so `hull` names a generated stand-in instead,
+// assets/eve/<hull>.obj with <hull>_no.png, <hull>_ar.png and <hull>_pmdg.png
+// (tools/gen_assets.py, ensure_assets(eve=True)): groups Hull and Glass plus
+// one EveFilter discards, uvs, smooth normals, 256x256 textures. The caller
+// passes the palette with the hull: the reference's Stratios and Nestor both
+// take EveMaterialColor::soe(); the stand-ins take soe() and ore()
+// (eve.rs:166-188), so the scene shows both.
+Model load_ship(World& world, const std::string& assets, const std::string& hull, const EveMaterialColor& colors) {
+  const std::string base = join_path(assets, "eve/" + hull);
+  Material material = EveMaterial(Texture::load_png(base + "_no.png", WrapMode::Repeat),
+                                  Texture::load_png(base + "_ar.png", WrapMode::Repeat),
+                                  Texture::load_png(base + "_pmdg.png", WrapMode::Repeat), colors);
+  // EveFilter::include_group (eve.rs:12-29)
+  static const std::vector<std::string> eve_filter = {"Hull", "hull", "Glass", "glass", "DarkHull", "exhaust", "Exhaust"};
+  ObjResult obj = load_obj(base + ".obj", &eve_filter);
+  std::vector<Triangle> tris;
+  tris.reserve(obj.faces.size());
+  for (const ObjFace& f : obj.faces)
+    tris.push_back(Triangle::with_norms_and_uvs(material, f.c[0].v, f.c[0].n, f.c[0].uv, f.c[1].v, f.c[1].n, f.c[1].uv,
+                                                f.c[2].v, f.c[2].n, f.c[2].uv));
+  return world.model(std::move(tris));
+}
+
+// scenes/eve.rs:21-97, line by line; the scene stream's draws in its order
+// (V3::rand() = x, y, z; one f32::rand() per fleet cell, three more where the
+// cell is kept).
+SceneResult eve(float aspect, const std::string& assets, uint64_t seed) {
+  SceneResult r;
+  r.world = std::make_unique<World>(environment(assets, "wormhole_class_05", V3{0, 0, 0}), seed);
+  World& world = *r.world;
+  auto v3_rand = [&world] {
+    float x = world.rand_f32(), y = world.rand_f32(), z = world.rand_f32();
+    return V3{x, y, z};
+  };
+  Model venture = load_ship(world, assets, "stratios", EveMaterialColor::soe());  // Hull::Stratios
+  Model orca = load_ship(world, assets, "nestor", EveMaterialColor::ore());       // Hull::Nestor
+
+  V3 orca_pos{-1250.0f, 5.0f, 0.0f};
+  world.add(orca.instance(orca_pos, V3{0, 0, 0} + ((v3_rand() - fill3(0.5f)) / 60.0f), fill3(1.0f)));
+
+  world.add(VolumeDesc{orca_pos, 1700.0f, 0.0006f, fill3(0.4f)});
+
+  world.add(Sphere(DiffuseLight(V3{4.0f, 4.0f, 5.0f} * 10.0f), V3{10000.0f, -4000.0f, 4800.0f}, 1500.0f));
+
+  V3 look_from{0.0f, -20.0f, 500.0f};
+  V3 rotation{-0.03f, 0.0f, 0.0f};
+  for (int xi = 0; xi < 6; ++xi) {
+    for (int zi = 0; zi < 6; ++zi) {
+      float x = ((float)xi - 3.0f) * 190.0f;
+      float z = ((float)zi - 3.0f) * 190.0f;
+      float y = (world.rand_f32() * 2.0f - 1.0f) * 150.0f;
+      V3 pos{x, y, z};
+      V3 dv = pos - look_from;
+      if (sqrtf(dot(dv, dv)) > 50.0f)
+        world.add(venture.instance(pos, rotation + ((v3_rand() - fill3(0.5f)) / 30.5f), fill3(0.2f)));
+    }
+  }
+  V3 look_at = orca_pos;
+  float focus_distance = length(look_from - look_at);
+  r.camera = Camera::make(50.0f, look_from, look_at, V3{0, 1, 0}, aspect, 0.2f, focus_distance);
+  return r;
+}
+
 }  // namespace
 
 SceneResult generate_builtin(const std::string& name, float aspect, const std::string& assets, uint64_t seed,
@@ -257,6 +326,8 @@ SceneResult generate_builtin(const std::string& name, float aspect, const std::s
     r = menger(aspect, assets, seed, 5);
   else if (name == "menger_l3")
     r = menger(aspect, assets, seed, 3);
+  else if (name == "eve")
+    r = eve(aspect, assets, seed);
   else
     throw Error(MRT_ERR_INVALID, "unknown built-in scene '" + name + "'");
   if (top_level)

@@ -191,6 +191,18 @@ uint32_t World::intern_material(const Material& m) {
     d.left = intern_material(*m.left);
     d.right = intern_material(*m.right);
   }
+  if (m.kind == MRT_MAT_EVE) {  // `surface` names its record in the Eve table
+    mrt_eve_material e{};
+    e.normal_occlusion = intern_texture(m.normal_occlusion);
+    e.albedo_roughness = intern_texture(m.albedo_roughness);
+    e.pmdg = intern_texture(m.pmdg);
+    for (int k = 0; k < 4; ++k) put3(e.colors + 3 * k, m.colors[k]);
+    put3(e.glow, m.glow);
+    size_t at = 0;
+    while (at < eve_materials_.size() && memcmp(&eve_materials_[at], &e, sizeof(e)) != 0) ++at;
+    if (at == eve_materials_.size()) eve_materials_.push_back(e);
+    d.surface = (uint32_t)at;
+  }
   std::string key((const char*)&d, sizeof(d));
   auto it = material_index_.find(key);
   if (it != material_index_.end()) return it->second;
@@ -406,6 +418,12 @@ const mrt_scene_desc& World::desc() {
   desc_.volumes = volumes_.data();
   desc_.n_volumes = (uint32_t)volumes_.size();
   return desc_;
+}
+
+const mrt_scene_ext& World::desc_ext() {
+  ext_.eve_materials = eve_materials_.data();
+  ext_.n_eve_materials = (uint32_t)eve_materials_.size();
+  return ext_;
 }
 
 }  // namespace massrt

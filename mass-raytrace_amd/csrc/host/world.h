@@ -113,6 +113,10 @@ struct Material {
   float param = 0.0f;
   V3 emit{0, 0, 0};                             // DiffuseLight emission / Isotrophic albedo
   std::shared_ptr<const Material> left, right;  // Mix
+  // EveMaterial (eve.rs:31-36): normal+occlusion, albedo+roughness, paint/material/dirt/glow
+  SharedTexture normal_occlusion, albedo_roughness, pmdg;
+  std::array<V3, 4> colors{};  // EveMaterialColor::colors
+  V3 glow{0, 0, 0};
 };
 inline Material NoMaterial() { return Material{}; }  // impl Material for ()
 inline Material Lambertian(Surface s) {
@@ -153,6 +157,30 @@ inline Material Mix(float ratio, Material l, Material r) {  // material.rs:396-4
   m.param = ratio;
   m.left = std::make_shared<const Material>(std::move(l));
   m.right = std::make_shared<const Material>(std::move(r));
+  return m;
+}
+// EveMaterialColor (eve.rs:136-188)
+struct EveMaterialColor {
+  std::array<V3, 4> colors;
+  V3 glow;
+  static EveMaterialColor ore() {
+    return {{V3{0.02f, 0.02f, 0.02f}, V3{0.1f, 0.1f, 0.1f}, V3{0.15f, 0.26f, 0.39f}, V3{0.85f, 0.62f, 0.2f}},
+            V3{0.5f, 0.85f, 2.0f}};
+  }
+  static EveMaterialColor soe() {
+    return {{V3{0.02f, 0.02f, 0.02f}, V3{0.2f, 0.2f, 0.2f}, V3{1.0f, 1.0f, 1.0f}, V3{0.5f, 0.0f, 0.0f}},
+            V3{0.5f, 0.85f, 2.0f}};
+  }
+};
+// EveMaterial::new (eve.rs:44-64); the textures are loaded with WrapMode::Repeat
+inline Material EveMaterial(SharedTexture no, SharedTexture ar, SharedTexture pmdg, const EveMaterialColor& c) {
+  Material m;
+  m.kind = MRT_MAT_EVE;
+  m.normal_occlusion = std::move(no);
+  m.albedo_roughness = std::move(ar);
+  m.pmdg = std::move(pmdg);
+  m.colors = c.colors;
+  m.glow = c.glow;
   return m;
 }
 inline Material DiffuseLight(V3 emit) {
@@ -313,6 +341,8 @@ class World {
   void set_background(Background bg) { background_ = std::move(bg); }
   // flatten into the C ABI description (pointers valid until modified)
   const mrt_scene_desc& desc();
+  // the tables beside it (mrt_upload_scene_ext); call after desc()
+  const mrt_scene_ext& desc_ext();
 
   size_t n_objects() const { return objects_.size(); }
   size_t n_nodes() const { return nodes_.size(); }
@@ -332,6 +362,8 @@ class World {
   std::vector<mrt_model> models_;
   std::vector<mrt_volume> volumes_;
   std::vector<mrt_material> materials_;
+  std::vector<mrt_eve_material> eve_materials_;
+  mrt_scene_ext ext_{};
   std::vector<mrt_surface> surfaces_;
   std::vector<mrt_texture> textures_;
   std::vector<SharedTexture> texture_refs_;
@@ -360,7 +392,9 @@ struct ObjResult {
   std::vector<ObjFace> faces;
   std::string material_library;  // resolved path ("" if none)
 };
-ObjResult load_obj(const std::string& path);
+// groups: ObjLoader::with_filter of "the group is listed" (obj_loader.rs:348,394-397,431-436);
+// null: no filter
+ObjResult load_obj(const std::string& path, const std::vector<std::string>* groups = nullptr);
 // PNG -> RGBA8 (image::io::Reader + to_rgba8, texture.rs:36-39)
 bool decode_png(const std::string& path, std::vector<uint8_t>& rgba, uint32_t& w, uint32_t& h, std::string& err);
 

@@ -47,7 +47,12 @@ int main(int argc, char** argv) {
   }
   mrt_ctx* ctx = nullptr;
   if (mrt_create(device, &ctx) != MRT_OK) return fail("mrt_create", nullptr);
-  if (mrt_upload_scene(ctx, &desc) != MRT_OK) return fail("mrt_upload_scene", ctx);
+  mrt_scene_ext ext;  // the Eve table, empty for the other scenes
+  if (mrt_builder_desc_ext(b, &ext) != MRT_OK) {
+    std::fprintf(stderr, "desc_ext: %s\n", mrt_builder_last_error());
+    return 1;
+  }
+  if (mrt_upload_scene_ext(ctx, &desc, &ext) != MRT_OK) return fail("mrt_upload_scene_ext", ctx);
   if (mrt_set_camera(ctx, &cam) != MRT_OK) return fail("mrt_set_camera", ctx);
   mrt_builder_free(b);
 

@@ -58,7 +58,9 @@ int main(int argc, char** argv) {
 
   mrt_ctx* ctx = nullptr;
   if (mrt_create_multi((int)devs.size(), devs.data(), &ctx) != MRT_OK) die("mrt_create_multi", nullptr);
-  if (mrt_upload_scene(ctx, &desc) != MRT_OK) die("mrt_upload_scene", ctx);
+  mrt_scene_ext ext;  // the Eve table, empty for the other scenes
+  if (mrt_builder_desc_ext(b, &ext) != MRT_OK) die("mrt_builder_desc_ext", nullptr);
+  if (mrt_upload_scene_ext(ctx, &desc, &ext) != MRT_OK) die("mrt_upload_scene_ext", ctx);
   if (mrt_set_camera(ctx, &cam) != MRT_OK) die("mrt_set_camera", ctx);
   mrt_builder_free(b);
   mrt_image* img = nullptr;

@@ -30,6 +30,7 @@ REPO = _HERE.parent.parent
 ABI_VERSION = 9  # MRT_ABI_VERSION this binding was written for
 REF_NONE, REF_NODE, REF_SPHERE, REF_TRIANGLE, REF_INSTANCE, REF_MODEL, REF_VOLUME = range(7)
 MAT_NONE, MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_DIFFUSE_LIGHT, MAT_SPECULAR, MAT_ISOTROPHIC, MAT_MIX = range(8)
+MAT_EVE = 8  # EveMaterial (eve.rs:31-134): Builder.eve_material
 WRAP_MIRROR, WRAP_REPEAT, WRAP_CLAMP = range(3)
 BG_SOLID, BG_SKY, BG_SKYSPHERE, BG_CUBEMAP = range(4)
 SURF_SOLID, SURF_TEXTURE, SURF_YCBCR, SURF_BLEND, SURF_FALLBACK = range(5)
@@ -110,6 +111,31 @@ class MrtSceneDesc(C.Structure):
         ("background", MrtBackground),
         ("volumes", C.c_void_p), ("n_volumes", C.c_uint32),
     ]
+
+
+class MrtEveMaterial(C.Structure):
+    _fields_ = [("normal_occlusion", C.c_uint32), ("albedo_roughness", C.c_uint32), ("pmdg", C.c_uint32),
+                ("colors", C.c_float * 12), ("glow", C.c_float * 3)]
+
+
+class MrtSceneExt(C.Structure):
+    _fields_ = [("eve_materials", C.POINTER(MrtEveMaterial)), ("n_eve_materials", C.c_uint32)]
+
+
+SHADE_FRONT_FACE, SHADE_HAS_UV, SHADE_SCATTERED = 1, 2, 4
+
+
+class MrtShadeOut(C.Structure):
+    _fields_ = [("prim", C.c_uint32), ("container", C.c_uint32), ("t", C.c_float), ("flags", C.c_uint32),
+                ("point", C.c_float * 3), ("normal", C.c_float * 3), ("uv", C.c_float * 2),
+                ("material", C.c_uint32), ("emitted", C.c_float * 3), ("attenuation", C.c_float * 3),
+                ("direction", C.c_float * 3)]
+
+
+# mrt_shade_out as a numpy record (Context.shade_rays)
+SHADE_DTYPE = np.dtype([("prim", "<u4"), ("container", "<u4"), ("t", "<f4"), ("flags", "<u4"), ("point", "<f4", 3),
+                        ("normal", "<f4", 3), ("uv", "<f4", 2), ("material", "<u4"), ("emitted", "<f4", 3),
+                        ("attenuation", "<f4", 3), ("direction", "<f4", 3)])
 
 
 class MrtCamera(C.Structure):
@@ -228,6 +254,8 @@ EXPORTED_SYMBOLS = [
     "mrt_build_info", "mrt_set_option", "mrt_get_option", "mrt_get_tuning", "mrt_context_transport", "mrt_image_gather",
     "mrt_debug_rccl_library", "mrt_debug_transport", "mrt_image_device_stats",
     "mrt_denoise_default_params", "mrt_denoise_device", "mrt_denoise", "mrt_image_set_denoise",
+    "mrt_upload_scene_ext", "mrt_shade_rays", "mrt_builder_eve_material", "mrt_builder_desc_ext",
+    "mrt_load_obj_groups",
 ]
 
 _lib = None
@@ -325,6 +353,11 @@ def lib() -> C.CDLL:
         "mrt_denoise_device": (I, [P, U32, U32, P, U32, P, P, C.POINTER(MrtDenoiseParams), P, P]),
         "mrt_denoise": (I, [P, U32, U32, fp, U32, fp, fp, C.POINTER(MrtDenoiseParams), fp]),
         "mrt_image_set_denoise": (I, [P, C.POINTER(MrtDenoiseParams)]),
+        "mrt_upload_scene_ext": (I, [P, C.POINTER(MrtSceneDesc), C.POINTER(MrtSceneExt)]),
+        "mrt_shade_rays": (I, [P, fp, U32, F, F, U64, C.POINTER(MrtShadeOut)]),
+        "mrt_builder_eve_material": (I, [P, U32, U32, U32, fp, fp]),
+        "mrt_builder_desc_ext": (I, [P, C.POINTER(MrtSceneExt)]),
+        "mrt_load_obj_groups": (I64, [C.c_char_p, C.POINTER(C.c_char_p), U32, fp, U64]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -413,6 +446,13 @@ class Builder:
     def material(self, kind, surface=0, param=0.0, emit=(0.0, 0.0, 0.0)) -> int:
         return _check_builder(lib().mrt_builder_material(self.h, kind, surface, param, *emit))
 
+    def eve_material(self, no_surface, ar_surface, pmdg_surface, colors, glow) -> int:
+        """EveMaterial::new over three texture surfaces (eve.rs:44-64); colors: 4 x rgb, glow: rgb."""
+        c = np.ascontiguousarray(np.asarray(colors, dtype=np.float32).reshape(12))
+        g = _f3(glow)
+        return _check_builder(lib().mrt_builder_eve_material(self.h, no_surface, ar_surface, pmdg_surface, _fptr(c),
+                                                             _fptr(g)))
+
     def mix(self, ratio, left, right) -> int:
         """Mix::new(ratio, left, right) (material.rs:391-426)."""
         return _check_builder(lib().mrt_builder_mix(self.h, ratio, left, right))
@@ -481,6 +521,13 @@ class Builder:
         if lib().mrt_builder_desc(self.h, C.byref(d), C.byref(cam)) != 0:
             raise MassrtError(lib().mrt_builder_last_error().decode())
         return d, cam
+
+    def desc_ext(self) -> MrtSceneExt:
+        """The tables beside the description (mrt_upload_scene_ext)."""
+        e = MrtSceneExt()
+        if lib().mrt_builder_desc_ext(self.h, C.byref(e)) != 0:
+            raise MassrtError(lib().mrt_builder_last_error().decode())
+        return e
 
     def desc_only(self) -> MrtSceneDesc:
         d = MrtSceneDesc()
@@ -609,11 +656,15 @@ class Context:
 
     def upload(self, builder: Builder):
         d, cam = builder.desc()
-        self._check(lib().mrt_upload_scene(self.h, C.byref(d)))
+        ext = builder.desc_ext()
+        self._check(lib().mrt_upload_scene_ext(self.h, C.byref(d), C.byref(ext)))
         self._check(lib().mrt_set_camera(self.h, C.byref(cam)))
 
-    def upload_desc(self, desc: MrtSceneDesc):
-        self._check(lib().mrt_upload_scene(self.h, C.byref(desc)))
+    def upload_desc(self, desc: MrtSceneDesc, ext: MrtSceneExt | None = None):
+        if ext is None:
+            self._check(lib().mrt_upload_scene(self.h, C.byref(desc)))
+        else:
+            self._check(lib().mrt_upload_scene_ext(self.h, C.byref(desc), C.byref(ext)))
 
     def set_camera(self, cam: MrtCamera):
         self._check(lib().mrt_set_camera(self.h, C.byref(cam)))
@@ -653,6 +704,16 @@ class Context:
         self._check(lib().mrt_trace_rays(self.h, _fptr(r), n, t_min, t_max, out))
         a = np.frombuffer(out, dtype=np.uint32).reshape(-1, 4)[:n].copy()
         return a  # columns: prim, container, t bits, front_face
+
+    def shade_rays(self, rays: np.ndarray, t_min=0.001, t_max=float("inf"), seed=1) -> np.ndarray:
+        """Hit, Hit::emit and Hit::scatter of explicit rays (mrt_shade_rays):
+        one SHADE_DTYPE record per ray."""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        n = r.shape[0]
+        out = np.zeros(max(n, 1), dtype=SHADE_DTYPE)
+        self._check(lib().mrt_shade_rays(self.h, _fptr(r), n, t_min, t_max, seed,
+                                         out.ctypes.data_as(C.POINTER(MrtShadeOut))))
+        return out[:n]
 
     def counters(self) -> dict:
         c = MrtCounters()
@@ -817,6 +878,19 @@ def load_obj(path) -> np.ndarray:
         raise MassrtError(lib().mrt_builder_last_error().decode())
     out = np.zeros((n, 24), dtype=np.float32)
     lib().mrt_load_obj(str(path).encode(), _fptr(out), n)
+    return out
+
+
+def load_obj_groups(path, groups) -> np.ndarray:
+    """load_obj keeping only the faces of the listed `o`/`g` groups
+    (ObjLoader::with_filter, obj_loader.rs:431-436); no groups: everything."""
+    names = [g.encode() for g in groups]
+    arr = (C.c_char_p * max(len(names), 1))(*names)
+    n = lib().mrt_load_obj_groups(str(path).encode(), arr, len(names), None, 0)
+    if n < 0:
+        raise MassrtError(lib().mrt_builder_last_error().decode())
+    out = np.zeros((n, 24), dtype=np.float32)
+    lib().mrt_load_obj_groups(str(path).encode(), arr, len(names), _fptr(out), n)
     return out
 
 

@@ -13,6 +13,12 @@
                        models/environments/ PNGs are not in the reference):
                        stars01_tile2.png (RGBA star tile) and j02/{0..5}.png (8-bit
                        grey luma) + j02/{0..5}_chroma.png (RGB chroma), 256x256
+  eve/                 stand-ins for the hulls eve::load_ship reads (eve.rs:216-340,
+                       proprietary, not in the reference): stratios.obj and nestor.obj
+                       (v/vt/vn; groups Hull, Glass and Antenna, which EveFilter
+                       discards; a few thousand triangles) with <hull>_no.png,
+                       <hull>_ar.png, <hull>_pmdg.png (256x256 RGBA), and the
+                       environment "wormhole_class_05" beside j02
 
 Usage: python tools/gen_assets.py [--out assets] [--all]
 """
@@ -177,8 +183,84 @@ def ensure_environment(out: Path, name: str = "j02"):
             write_png(d / f"{f}_chroma.png", chroma)
 
 
+def hull_obj(path: Path, length: float, radius: float, seed: int):
+    """A ship-like closed surface as OBJ with v/vt/vn: group Hull (a tapered,
+    dented ellipsoid, 48 x 30 quads), group Glass (a dome on its back, 16 x 8),
+    group Antenna (a thin spike, 8 x 4: EveFilter discards it); faces index
+    the one global vertex list, so Antenna's vertices still count."""
+    rng = np.random.default_rng(seed)
+    bumps = rng.uniform(-1.0, 1.0, size=6)
+
+    def patch(nu, nv, pos):
+        u = np.linspace(0.0, 1.0, nu + 1)
+        v = np.linspace(0.0, 1.0, nv + 1)
+        U, V = np.meshgrid(u, v, indexing="ij")
+        P = pos(U, V)
+        e = 1e-4
+        N = np.cross(pos(U, V + e) - pos(U, V - e), pos(U + e, V) - pos(U - e, V))
+        N /= np.maximum(np.linalg.norm(N, axis=-1, keepdims=True), 1e-20)
+        i, j = np.meshgrid(np.arange(nu), np.arange(nv), indexing="ij")
+        a, b = i * (nv + 1) + j, (i + 1) * (nv + 1) + j
+        F = np.concatenate([np.stack([a, b, b + 1], -1).reshape(-1, 3), np.stack([a, b + 1, a + 1], -1).reshape(-1, 3)])
+        return P.reshape(-1, 3), N.reshape(-1, 3), np.stack([U * 2.0, V], -1).reshape(-1, 2), F
+
+    def ellipsoid(cx, cy, lx, ry, rz, th0, th1, dent):
+        def pos(U, V):
+            phi, th = U * 2.0 * np.pi, th0 + (th1 - th0) * V
+            taper = 1.0 + dent * (bumps[0] * np.sin(3.0 * th) + bumps[1] * np.cos(5.0 * phi) * np.sin(th))
+            return np.stack([cx + lx * np.cos(th), cy + ry * taper * np.sin(th) * np.cos(phi),
+                             rz * taper * np.sin(th) * np.sin(phi)], -1)
+        return pos
+
+    parts = [("Hull", patch(48, 30, ellipsoid(0.0, 0.0, length / 2, radius, radius * 1.4, 0.04, np.pi - 0.04, 0.12))),
+             ("Antenna", patch(8, 4, ellipsoid(length * 0.3, radius * 1.5, radius * 0.1, radius * 1.2, radius * 0.05,
+                                              0.2, np.pi - 0.2, 0.0))),
+             ("Glass", patch(16, 8, ellipsoid(length * 0.15, radius * 0.7, length * 0.12, radius * 0.6, radius * 0.5,
+                                              0.1, np.pi - 0.1, 0.0)))]
+    with open(path, "w") as f:
+        f.write("# massrt synthetic hull (v/vt/vn)\n")
+        base = 0
+        for k, (name, (P, N, UV, F)) in enumerate(parts):
+            f.write(("o " if k % 2 == 0 else "g ") + name + "\n")  # groups by `o` and by `g`
+            buf = io.StringIO()
+            np.savetxt(buf, P, fmt="v %.7g %.7g %.7g")
+            np.savetxt(buf, UV, fmt="vt %.7g %.7g")
+            np.savetxt(buf, N, fmt="vn %.7g %.7g %.7g")
+            np.savetxt(buf, np.repeat(F + 1 + base, 3, axis=1), fmt="f %d/%d/%d %d/%d/%d %d/%d/%d")
+            f.write(buf.getvalue())
+            base += P.shape[0]
+
+
+def hull_textures(seed: int, n: int = 256):
+    """(normal+occlusion, albedo+roughness, paint/material/dirt/glow), RGBA8 n x n each.
+    The normal sits in G and A (eve.rs:66-73), occlusion in B."""
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:n, 0:n].astype(np.float64) / n
+    panels = (np.floor(x * 8) + np.floor(y * 8)) % 2
+    coarse = rng.random((n // 16, n // 16)).repeat(16, 0).repeat(16, 1)
+    one = np.ones_like(x)
+    no = np.stack([0.5 * one, 0.5 + 0.18 * np.sin(2 * np.pi * x * 8), 0.6 + 0.4 * coarse,
+                   0.5 + 0.18 * np.cos(2 * np.pi * y * 8)], -1)
+    ar = np.stack([0.55 + 0.3 * panels, 0.5 + 0.3 * coarse, 0.45 + 0.3 * (1 - panels), 0.15 + 0.7 * coarse], -1)
+    glow = ((np.floor(x * 32) % 8 == 3) & (np.floor(y * 32) % 8 == 5)).astype(np.float64)
+    pmdg = np.stack([0.2 + 0.6 * panels, np.floor(coarse * 4) / 3.0 * 0.999, 0.25 * rng.random((n, n)) * coarse, glow], -1)
+    return [(np.clip(t, 0, 1) * 255 + 0.5).astype(np.uint8) for t in (no, ar, pmdg)]
+
+
+def ensure_eve(out: Path, publish):
+    (out / "eve").mkdir(parents=True, exist_ok=True)
+    ensure_environment(out, "wormhole_class_05")
+    for k, (hull, length, radius) in enumerate((("stratios", 260.0, 40.0), ("nestor", 620.0, 90.0))):
+        publish(f"eve/{hull}.obj", lambda p, a=(length, radius, 40 + k): hull_obj(p, *a))
+        tex = None
+        for i, suffix in enumerate(("no", "ar", "pmdg")):
+            if not (out / f"eve/{hull}_{suffix}.png").exists():
+                tex = tex or hull_textures(50 + k)
+                publish(f"eve/{hull}_{suffix}.png", lambda p, t=tex[i]: write_png(p, t))
+
+
 def ensure_assets(out: Path | str = DEFAULT_DIR, mesh: bool = True, textures: bool = False,
-                  environment: bool = False) -> Path:
+                  environment: bool = False, eve: bool = False) -> Path:
     """Generate the missing assets under `out`. Safe to call from several
     processes at once (pytest -n, ranks): one holds an exclusive lock while it
     writes, every file appears by rename only when complete."""
@@ -188,20 +270,22 @@ def ensure_assets(out: Path | str = DEFAULT_DIR, mesh: bool = True, textures: bo
     out.mkdir(parents=True, exist_ok=True)
     with open(out / ".lock", "w") as lk:
         fcntl.flock(lk, fcntl.LOCK_EX)
-        _ensure_locked(out, mesh, textures, environment)
+        _ensure_locked(out, mesh, textures, environment, eve)
     return out
 
 
-def _ensure_locked(out: Path, mesh: bool, textures: bool, environment: bool) -> None:
+def _ensure_locked(out: Path, mesh: bool, textures: bool, environment: bool, eve: bool = False) -> None:
     def publish(name, write):
         if not (out / name).exists():
-            tmp = out / f".tmp{os.getpid()}_{name}"
+            tmp = out / f".tmp{os.getpid()}_{name.replace('/', '_')}"
             write(tmp)
             tmp.rename(out / name)
 
     publish("cube.ply", lambda p: shutil.copy(REPO / "tests" / "golden" / "cube.ply", p))
     if environment:
         ensure_environment(out)
+    if eve:
+        ensure_eve(out, publish)
     if mesh and not ((out / "mesh_1m.ply").exists() and (out / "mesh_1m.obj").exists()):
         P, N, UV = torus_grid()
         F = torus_faces()
