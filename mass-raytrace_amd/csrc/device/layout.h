@@ -86,12 +86,17 @@ constexpr uint32_t kTriIdMask = 0x0FFFFFFFu;
 //           parent: its reference world parent box (vnf_leaf's, for nf_finish)
 constexpr uint32_t kNfIdx = 0x0FFFFFFFu;  // index bits of an NF node's children base
 // an NF node's slot1.w: its left / right child's subtree holds a "wild"
-// instance, whose rounding the world margin does not cover (nf_tree.cpp): the
-// node's boxes are thickened by the wild margin too (nf_bound.h nf_rho_wild)
+// instance, whose rounding the world margin does not cover (nf_tree.cpp). A
+// forced child is never culled by the node's box test and carries no exit
+// bound; the wild leaf's own test (walk_nf.h nf_wild_enter: its world box
+// under its own margin) decides. The wild instances have a tree of their own
+// (DevScene::nf_wild_root), all of it forced; the world tree carries no flag.
 constexpr uint32_t kNfForceL = 0x10000000u, kNfForceR = 0x20000000u;
 constexpr uint32_t kNfPop = 0x0FFFFFFFu;  // "next" of a leaf's last record: pop the stack
 constexpr int kNfExpMin = -100;            // smallest plane step 2^e (products with 1/d stay normal)
-constexpr uint32_t kNfStack = 24u;         // stack entries per lane (LDS): the trees' depth is capped to fit
+// stack entries per lane (LDS): the trees' depth is capped to fit. The bottom
+// entry is the wild tree's root while the world tree is walked (walk.h nf_start).
+constexpr uint32_t kNfStack = 25u;
 constexpr uint32_t kNfWildFew = 16u;       // a world of at most this many instances may leave big absolute terms out of its margin (nf_tree.cpp)
 constexpr uint32_t kNoParent = 0xFFFFFFFFu;
 // Verification record of a leaf object (DevScene::vnf_leaf[vnf_base[kind] + id]):
@@ -200,6 +205,7 @@ struct DevScene {
   uint32_t tl_world_begin;     // world entry index beside the treelet (possibly LDS-tagged)
   // verified near-first trees (nf_ok == 0: the scene has none)
   uint32_t nf_ok, nf_world;    // the NF world tree's root record
+  uint32_t nf_wild_root;       // the wild instances' own tree, walked last (0: none, or it is nf_world)
   const uint32_t* vnf_leaf;    // {reference parent box, order key} pairs per leaf object
   uint32_t vnf_base[4];        // first vnf_leaf entry of spheres, triangles, instances, models
   uint32_t n_vnf;

@@ -251,9 +251,12 @@ struct Tree {
     nodes[id].l = l, nodes[id].r = r, nodes[id].axis = (uint32_t)axis;
     return id;
   }
-  // every node flags its child whose subtree holds a wild item (the nodes on
-  // the path from the root to each wild leaf thicken their boxes by the wild
-  // margin too); returns whether node n's subtree holds one
+  // every node flags its child whose subtree holds a wild item: the walk
+  // never culls a flagged child and keeps no exit bound for it (the world
+  // margin, which thickens the node's boxes, does not cover a wild item's
+  // hits); each wild leaf's own box test decides instead. Run on the wild
+  // items' own tree, where it flags every child. Returns whether node n's
+  // subtree holds a wild item.
   bool mark_forced(int32_t n) {
     Node& x = nodes[n];
     if (x.l < 0) {
@@ -727,14 +730,15 @@ struct Builder {
     // of the world tree, an instance's successor and its return marker, a far
     // child per BLAS level — kept within kNfStack by capping the depth (median
     // splits at the cap's edge): the BLAS trees first, leaving the world tree
-    // at least the levels a balanced tree over its objects needs (and one for
-    // the wild instances' subtree)
+    // at least the levels a balanced tree over its objects needs, and one
+    // word for the wild tree's root, which lies at the stack's bottom while
+    // the world tree is walked (walk.h nf_start)
     const uint32_t has_blas = s.blas_regions.empty() ? 0 : 2;
     std::vector<Tree> blas(s.blas_regions.size());
     blas_box.assign(s.blas_regions.size(), Box{});
     blas_bound.assign(s.blas_regions.size(), TriBound{});
     uint32_t blas_depth = 0;
-    const uint32_t world_min = Tree::min_levels((uint32_t)world_objs.size());
+    const uint32_t world_min = Tree::min_levels((uint32_t)world_objs.size()) + 1;
     if (world_min + has_blas > kNfStack) return (s.nf_note = "too many world objects for the walk's stack", true);
     for (size_t k = 0; k < blas.size(); ++k) {
       for (uint32_t r : blas_objs[k]) {
@@ -808,20 +812,47 @@ struct Builder {
     }
     aw0 = std::max(aw0, world_tri.a0), aw1 = std::max(aw1, world_tri.a1);
     if (r_min < 0x1p-60) return (s.nf_note = "a sphere too small for the walk's rounding bound", true);
+    // The world tree holds the other items only: no forced path, and its
+    // boxes do not span the wild items' boxes. The wild items get a tree of
+    // their own, every child of it forced, which a ray walks last — its root
+    // waits at the bottom of the stack (walk.h nf_start) — so each wild leaf's
+    // own test runs against the `best` of everything else. A world of wild
+    // items only has that tree as its world tree.
+    // Not beside a model: a model's BLAS is walked under the world ray, box
+    // after box, and a floor found first is the `best` that prunes it
+    // (mesh_ply's 1M triangles: 39.5 box tests per ray with the floor and the
+    // lights last against 37.5, and as many entries, tools/slab_check); spheres
+    // and instances cost the world tree a leaf test each.
+    Tree wild_tree;
+    bool has_model = false;
+    for (const Item& it : items) has_model = has_model || kind_of(w, it.rec) == KIND_MODEL;
+    const bool split = !wild_items.empty() && !items.empty() && !has_model;
+    const uint32_t below = has_blas ? 2 + blas_depth : 0;
     world.items = items;
-    world.items.insert(world.items.end(), wild_items.begin(), wild_items.end());
-    world.max_depth = kNfStack - (has_blas ? 2 + blas_depth : 0);
+    if (!split) world.items.insert(world.items.end(), wild_items.begin(), wild_items.end());
+    world.max_depth = kNfStack - below - 1;
     world.build(0, (uint32_t)world.items.size(), 0);
-    if (!wild_items.empty()) world.mark_forced(0);
+    if (split) {
+      wild_tree.items = wild_items;
+      wild_tree.max_depth = kNfStack - below;
+      wild_tree.build(0, (uint32_t)wild_tree.items.size(), 0);
+      wild_tree.mark_forced(0);
+    } else if (!wild_items.empty()) {
+      world.mark_forced(0);
+    }
     if (aw1 > 0 || ao1 > 0)  // generic triangles somewhere: every tree's nodes get their cones
       for (Tree* t : [&] {
              std::vector<Tree*> v{&world};
+             if (split) v.push_back(&wild_tree);
              for (Tree& b : blas) v.push_back(&b);
              return v;
            }())
         fit_cones(*t);
-    s.nf_stack_need = world.depth + (has_blas ? 2 + blas_depth : 0);
-    if (s.nf_stack_need > kNfStack) return (s.nf_note = "trees deeper than the walk's stack", true);
+    // the wild root's word lies below the world tree's entries; it is popped
+    // before the wild tree pushes its own
+    s.nf_stack_need = std::max(world.depth + (split ? 1u : 0u), wild_tree.depth) + below;
+    // without a wild tree the walk has kNfStack - 1 words (trace.hip launch_trace): the marker's stays unused
+    if (s.nf_stack_need > kNfStack - (split ? 0u : 1u)) return (s.nf_note = "trees deeper than the walk's stack", true);
     // the constants (rounded up) of nf_bound.h
     auto ball = [](const Box& b, float c[3], float& rr) {
       double r2 = 0;
@@ -865,6 +896,11 @@ struct Builder {
     }
     s.nf_world = emit(world);
     if (s.nf_world == ~0u) return (s.nf_note = "a box the node format cannot hold (not finite)", true);
+    s.nf_wild_root = 0;
+    if (split) {  // after the world tree; one wild item: its leaf record alone
+      s.nf_wild_root = emit(wild_tree);
+      if (s.nf_wild_root == ~0u) return (s.nf_note = "a box the node format cannot hold (not finite)", true);
+    }
     for (size_t k = 0; k < blas.size(); ++k) {
       if (blas[k].items.empty()) continue;
       const uint32_t root = emit(blas[k]);
@@ -907,6 +943,7 @@ bool build_nf_trees(const mrt_scene_desc& d, HostScene& s, std::string& err) {
     s.slots.resize(keep);
     s.nf_boxes = 0;
     s.nf_wild = 0;
+    s.nf_wild_root = 0;
     s.nf_cones = 0;
     s.vnf_leaf.clear();
   }

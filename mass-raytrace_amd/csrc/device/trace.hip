@@ -32,10 +32,11 @@ constexpr uint32_t kStashQuads = 4;  // float4s per lane of the world-ray stash 
 // near child first with a per-lane stack in LDS (kNfStack x BLK words of
 // dynamic shared memory), the winner checked against the reference tree,
 // rays that fail the check walked again the reference's way.
-template <bool COUNT, bool LDS, uint32_t ALPHA, bool RNG, int BLK, bool NF = false>
+template <bool COUNT, bool LDS, uint32_t ALPHA, bool RNG, int BLK, bool NF = false, bool WILD = false>
 __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(NF ? (COUNT ? 1 : 5) : (ALPHA == 0 && !RNG && !COUNT ? 8 : 1)))) void k_trace(DevScene S, PathBufs in, uint4* hits, Ctrl* ctrl, uint32_t cur,
                                                   DevCounters* cnt, float tmin, float tmax, TraceTune tune) {
   static_assert(!NF || (!LDS && !RNG), "the near-first walk has no treelet and no traversal draws");
+  static_assert(!WILD || NF, "only the near-first walk has a wild tree");
   constexpr int R = 1;
   const uint32_t n = ctrl->active[cur];
   if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -101,7 +102,12 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(NF ? (COUNT
       for (int q = 0; q < R; ++q) {
         if (t[q].ray == kIdle) {
           const uint32_t r = off + lane_rank(idle[q]);
-          if (r < avail) trav_init<RNG, LDS>(tin, t[q], MRT_IDX(S, pool + r, n, 20), tmax, NF ? S.nf_world : 0xFFFFFFFFu);
+          if (r < avail) {
+            if constexpr (NF)
+              trav_init_nf<WILD>(tin, stk, t[q], MRT_IDX(S, pool + r, n, 20), tmax, S.nf_world);
+            else
+              trav_init<RNG, LDS>(tin, t[q], MRT_IDX(S, pool + r, n, 20), tmax);
+          }
         }
         off += (uint32_t)__popcll(idle[q]);
         live |= __ballot(t[q].ray != kIdle);
@@ -126,11 +132,11 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(NF ? (COUNT
         if ((uint32_t)__popcll(bm) < tune.box_min) return false;
         if (run_box) {
           if (NF && t[q].sp != kExactMode)
-            trav_box_index_nf<COUNT>(tin, stk, t[q], lc);
+            trav_box_index_nf<COUNT, WILD>(tin, stk, t[q], lc);
           else
             trav_box_index<COUNT>(tin, t[q], lc);
         }
-        if (run_box && (!NF || t[q].sp != kNfDone)) trav_fetch<LDS>(tin, t[q]);
+        if (run_box && (!NF || !nf_parked<WILD>(t[q]))) trav_fetch<LDS>(tin, t[q]);
         if (COUNT) {
           lc.wave_slots += lane_id() == 0 ? 64u : 0u;
           lc.lane_steps += run_box ? 1u : 0u;
@@ -152,7 +158,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(NF ? (COUNT
       // twice. Every pass steps a lane: while the run is on, tune.prim_run >=
       // tune.prim_batch (options.h derive_tuning), so its lanes have prim_go.
       for (;;) {
-        const bool busy = !t[q].done && (!NF || t[q].sp != kNfDone);
+        const bool busy = !t[q].done && (!NF || !nf_parked<WILD>(t[q]));
         const bool at_box = busy && trav_at_box(t[q]);
         const unsigned long long box_mask = __ballot(at_box);
         const unsigned long long prim_mask = __ballot(busy && !at_box);
@@ -164,17 +170,17 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(NF ? (COUNT
         const bool prim_go = (__popcll(prim_mask) >= tune.prim_batch || box_mask == 0) && busy && !at_box;
         if (box_go) {
           if (NF && t[q].sp != kExactMode)
-            trav_box_index_nf<COUNT>(tin, stk, t[q], lc);
+            trav_box_index_nf<COUNT, WILD>(tin, stk, t[q], lc);
           else
             trav_box_index<COUNT>(tin, t[q], lc);
         }
         if (prim_go) {
           if (NF && t[q].sp != kExactMode)
-            trav_prim_index_nf<COUNT, ALPHA>(tin, stk, t[q], lc);
+            trav_prim_index_nf<COUNT, ALPHA, WILD>(tin, stk, t[q], lc);
           else
             trav_prim_index<COUNT, ALPHA, RNG, LDS>(tin, t[q], lc);
         }
-        if ((box_go || prim_go) && !t[q].done && (!NF || t[q].sp != kNfDone)) trav_fetch<LDS>(tin, t[q]);
+        if ((box_go || prim_go) && !t[q].done && (!NF || !nf_parked<WILD>(t[q]))) trav_fetch<LDS>(tin, t[q]);
         if (COUNT) {
           lc.wave_slots += lane_id() == 0 ? 64u : 0u;
           lc.lane_steps += (box_go || prim_go) ? 1u : 0u;
@@ -187,6 +193,23 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(NF ? (COUNT
       // record) until tune.nf_batch of them can share one pass, or until no
       // lane is walking any more
       if (NF) {
+        // lanes that have walked everything but the wild instances' tree
+        // (walk_nf.h kNfWait) enter it as a batch, for the same reason: a
+        // wild leaf's box test, the entry and the exit are the walk's longest
+        // steps, and a wave pays for each once per pass, however few lanes
+        // take it. Entered one lane at a time, as each ray's stack ran out,
+        // they cost sphere_grid 15% of k_trace's time for 12% fewer box
+        // tests; batched at nf_batch, -2.5% (at half of it +1.8%, at a
+        // quarter +7%: DESIGN.md §5).
+        if (WILD) {
+          const bool wait = t[q].sp == kNfWait;
+          const unsigned long long wm = __builtin_amdgcn_ballot_w64(wait);
+          if (wm != 0 && ((uint32_t)__popcll(wm) >= tune.nf_batch ||
+                          __builtin_amdgcn_ballot_w64(!t[q].done && !nf_parked<WILD>(t[q])) == 0) && wait) {
+            nf_resume_wild(tin, t[q]);
+            trav_fetch<LDS>(tin, t[q]);
+          }
+        }
         const bool over = t[q].sp == kNfDone;
         const unsigned long long om = __builtin_amdgcn_ballot_w64(over);
         if (om != 0 && ((uint32_t)__popcll(om) >= tune.nf_batch ||
@@ -280,19 +303,19 @@ TraceFn trace_kernel_lds(int block) {
                         : k_trace<COUNT, true, ALPHA, RNG, kBlock>;
 }
 template <bool COUNT, uint32_t ALPHA>
-TraceFn trace_kernel_a(bool lds, bool rng, int block, bool nf) {
-  if (nf) return k_trace<COUNT, false, ALPHA, false, kBlock, true>;
+TraceFn trace_kernel_a(bool lds, bool rng, int block, bool nf, bool wild) {
+  if (nf) return wild ? k_trace<COUNT, false, ALPHA, false, kBlock, true, true> : k_trace<COUNT, false, ALPHA, false, kBlock, true, false>;
   if (lds) return rng ? trace_kernel_lds<COUNT, ALPHA, true>(block) : trace_kernel_lds<COUNT, ALPHA, false>(block);
   return rng ? k_trace<COUNT, false, ALPHA, true, kBlock> : k_trace<COUNT, false, ALPHA, false, kBlock>;
 }
 template <bool COUNT>
-TraceFn trace_kernel_c(bool lds, uint32_t alpha, bool rng, int block, bool nf) {
-  return alpha == 2   ? trace_kernel_a<COUNT, 2>(lds, rng, block, nf)
-         : alpha == 1 ? trace_kernel_a<COUNT, 1>(lds, rng, block, nf)
-                      : trace_kernel_a<COUNT, 0>(lds, rng, block, nf);
+TraceFn trace_kernel_c(bool lds, uint32_t alpha, bool rng, int block, bool nf, bool wild) {
+  return alpha == 2   ? trace_kernel_a<COUNT, 2>(lds, rng, block, nf, wild)
+         : alpha == 1 ? trace_kernel_a<COUNT, 1>(lds, rng, block, nf, wild)
+                      : trace_kernel_a<COUNT, 0>(lds, rng, block, nf, wild);
 }
-TraceFn trace_kernel(bool count, bool lds, uint32_t alpha, bool rng, int block, bool nf) {
-  return count ? trace_kernel_c<true>(lds, alpha, rng, block, nf) : trace_kernel_c<false>(lds, alpha, rng, block, nf);
+TraceFn trace_kernel(bool count, bool lds, uint32_t alpha, bool rng, int block, bool nf, bool wild) {
+  return count ? trace_kernel_c<true>(lds, alpha, rng, block, nf, wild) : trace_kernel_c<false>(lds, alpha, rng, block, nf, wild);
 }
 
 }  // namespace
@@ -324,10 +347,15 @@ void launch_trace(mrt_ctx* c, hipStream_t st, const Queue& q, const PathBufs& in
   const bool nf = t.use_nf, lds = !nf && c->facts.treelet;
   const uint32_t alpha = c->scene_alpha ? (c->scene_ext ? 2u : 1u) : 0u;
   const int block = lds ? t.trace_block : kBlock;
-  const TraceFn f = trace_kernel(count, lds, alpha, c->facts.trav_rng, block, nf);
+  // a scene with a wild tree (layout.h nf_wild_root) runs the variant that walks it last, in batches; the
+  // others compile none of that and keep 24 stack words (the builder leaves them the marker's word unused)
+  const bool wild = nf && c->S.nf_wild_root != 0;
+  const TraceFn f = trace_kernel(count, lds, alpha, c->facts.trav_rng, block, nf, wild);
   // dynamic LDS: the near-first stack (kNfStack words per lane), the treelet, or the world-ray stash (4 x 16 B per lane)
-  const size_t smem = nf ? (size_t)kNfStack * block * 4 : lds ? (size_t)c->S.n_tlet * 16 : (size_t)kStashQuads * block * 16;
-  // Near-first: kNfStack KiB of LDS per workgroup allow 6 waves per SIMD, its
+  const size_t smem = nf ? (size_t)(kNfStack - (wild ? 0u : 1u)) * block * 4 : lds ? (size_t)c->S.n_tlet * 16 : (size_t)kStashQuads * block * 16;
+  // Near-first: 24 KiB of LDS per workgroup of 256 lanes, kNfStack (25) with a
+  // wild tree, allow 6 workgroups per CU (6 x 25 = 150 of 160 KiB), i.e. 6
+  // waves per SIMD, its
   // registers (<= 128 VGPRs: the rounding margins' state and code, round 5,
   // would spill at 80) at least 4. Beside another queue the walk takes 3
   // WG/CU: its vector-memory unit is the shared limit, so more of its waves

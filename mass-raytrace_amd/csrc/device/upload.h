@@ -59,6 +59,7 @@ struct HostScene {
   std::string nf_note;  // why a scene has no NF trees
   NfBound nfb{};         // the walk's rounding margins (nf_bound.h, nf_tree.cpp)
   uint32_t nf_wild = 0;  // instances the world margin does not cover: never culled
+  uint32_t nf_wild_root = 0;  // their own tree's root record, walked after the world tree (0: none, or it is nf_world)
   uint32_t nf_cones = 0;  // NF nodes carrying a normal cone (nf_bound.h nf_cone_rg)
   // tools/slab_check: set before building to keep every leaf object's NF box
   // (6 floats per vnf_leaf slot: mn xyz, mx xyz) and which instances are wild
@@ -114,6 +115,7 @@ inline DevScene host_dev_scene(const HostScene& s) {
   S.bg_m = s.bg_m;
   S.nf_ok = s.nf_ok ? 1u : 0u;
   S.nf_world = s.nf_world;
+  S.nf_wild_root = s.nf_ok ? s.nf_wild_root : 0u;
   S.vnf_leaf = s.vnf_leaf.data();
   for (int k = 0; k < 4; ++k) S.vnf_base[k] = s.vnf_base[k];
   S.n_vnf = (uint32_t)(s.vnf_leaf.size() / 2);

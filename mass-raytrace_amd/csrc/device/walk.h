@@ -69,7 +69,7 @@ MRT_HD TRay tray_unstash(const TravIn& in) {
 // hit is recovered from that record when the ray finishes (trav_hit).
 constexpr uint32_t kNoRet = 0xFFFFFFFFu;
 constexpr uint32_t kRetInstance = 0x80000000u;
-constexpr uint32_t kExactMode = 0xFFFFu;  // Trav::sp of the reference's walk
+constexpr uint32_t kExactMode = 0xFFFDu;  // Trav::sp of the reference's walk (below walk_nf.h's kNfWait, kNfDone)
 
 struct Trav {
   TRay r;  // ray of the space being traversed (world, or instance object space)
@@ -173,10 +173,46 @@ MRT_HD void nf_margin(const TravIn& in, Trav& t) {
   const NfCoef c = obj ? nf_coef_object(B, t.r.o, t.r.a.b) : nf_coef_world(B, t.r.o, t.r.a.b);
   t.nfl = nf_line(B, c, nf_cull(t.best), obj ? B.ao0 : B.aw0, obj ? B.ao1 : B.aw1, t.r.a.b, t.r.d);
 }
-// the walk starts at the NF world tree (trav_init): rays its bound does not
-// cover take the reference's walk instead
-MRT_HD void nf_start(const TravIn& in, Trav& t) {
+// stack marker: the bottom entry of a near-first ray's stack in a scene with a
+// wild tree (layout.h nf_wild_root). Popped, it says that everything else is
+// walked and the wild tree waits (walk_nf.h nf_pop, kNfWait).
+constexpr uint32_t kNfWildMark = 0x80000001u;
+// the lane's stack of record indices (LDS; kNfStack entries, layout.h)
+struct NfStack {
+  uint32_t* p;  // this lane's entry 0
+  uint32_t stride;
+};
+MRT_HD void nf_push(const NfStack& k, Trav& t, uint32_t v) {
+  k.p[t.sp * k.stride] = v;
+  t.sp += 1;  // the builder bounds the depth (nf_stack_need <= kNfStack)
+}
+// A wave-uniform value moved to its vector register here, not before the
+// kernel's loop: hoisted, that register is live across the whole of k_trace,
+// which sits at its 96-VGPR cap, and a copy went to scratch memory (8 B per
+// lane; tools/kernel_resources.sh). Generates no instruction.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MRT_PIN_VGPR(x) asm volatile("" : "+v"(x))
+#else
+#define MRT_PIN_VGPR(x) (void)0
+#endif
+// the walk starts at the NF world tree (trav_init_nf): rays its bound does not
+// cover take the reference's walk instead, and push nothing. WILD (the scene
+// has a wild tree, layout.h nf_wild_root; k_trace's variant for such scenes):
+// the ray first pushes kNfWildMark. LIFO order pops it when everything else
+// is done, so a wild leaf, which nothing above it culls, has its own box test
+// (walk_nf.h nf_wild_enter) run against the `best` of all the rest. Any
+// visiting order is exact: culling uses the current `best`, never below the
+// final one, so every primitive whose computed t is <= cull(final best) is
+// tested. Scenes without a wild tree compile none of this.
+template <bool WILD>
+MRT_HD void nf_start(const TravIn& in, const NfStack& k, Trav& t) {
   if (nf_ray_ok(in.S.nfb, t.r.a.b)) {
+    if (WILD) {
+      uint32_t mark = kNfWildMark;
+      MRT_PIN_VGPR(mark);
+      nf_push(k, t, mark);
+      MRT_PIN_VGPR(t.best);  // the margin's cull(t_max) is computed here, per ray, not kept from before the loop
+    }
     nf_margin(in, t);
     t.nl = INFINITY;
   } else {
@@ -185,9 +221,11 @@ MRT_HD void nf_start(const TravIn& in, Trav& t) {
   }
 }
 
-// Start ray `ray` of the pool (World::intersect(ray, in.tmin, tmax)).
-template <bool RNG = false, bool LDS = false>
-MRT_HD void trav_init(const TravIn& in, Trav& t, uint32_t ray, float tmax, uint32_t start = 0xFFFFFFFFu) {
+// Start ray `ray` of the pool (World::intersect(ray, in.tmin, tmax)): on the
+// reference's walk (trav_init), or on the near-first walk at record `start`
+// with the lane's stack (trav_init_nf).
+template <bool RNG, bool LDS, bool NF, bool WILD>
+MRT_HD void trav_begin(const TravIn& in, const NfStack& stk, Trav& t, uint32_t ray, float tmax, uint32_t start) {
   if (RNG) {
     const uint4 q = in.rng[ray];
     t.rng = PathRng{(unsigned long long)q.x | ((unsigned long long)q.y << 32),
@@ -195,8 +233,8 @@ MRT_HD void trav_init(const TravIn& in, Trav& t, uint32_t ray, float tmax, uint3
   }
   t.r = world_ray(in, ray);
   t.ray = ray;
-  t.i = start == 0xFFFFFFFFu ? in.world_begin : start;  // the near-first walk starts at its own world tree
-  t.sp = start == 0xFFFFFFFFu ? kExactMode : 0u;
+  t.i = NF ? start : in.world_begin;  // the near-first walk starts at its own world tree
+  t.sp = NF ? 0u : kExactMode;
   t.t2 = INFINITY;
   t.ret = kNoRet;
   t.best = tmax;
@@ -206,8 +244,16 @@ MRT_HD void trav_init(const TravIn& in, Trav& t, uint32_t ray, float tmax, uint3
 #ifdef MRT_DEBUG_BOUNDS
   t.steps = 0;
 #endif
-  if (start != 0xFFFFFFFFu) nf_start(in, t);
+  if (NF) nf_start<WILD>(in, stk, t);
   trav_fetch<LDS>(in, t);
+}
+template <bool RNG = false, bool LDS = false>
+MRT_HD void trav_init(const TravIn& in, Trav& t, uint32_t ray, float tmax) {
+  trav_begin<RNG, LDS, false, false>(in, NfStack{nullptr, 0}, t, ray, tmax, 0u);  // no stack: NF = false never touches it
+}
+template <bool WILD>
+MRT_HD void trav_init_nf(const TravIn& in, const NfStack& stk, Trav& t, uint32_t ray, float tmax, uint32_t start) {
+  trav_begin<false, false, true, WILD>(in, stk, t, ray, tmax, start);
 }
 
 MRT_HD bool trav_at_box(const Trav& t) { return (int32_t)t.s1.w < 0; }  // kBoxFlag (layout.h)

@@ -16,39 +16,57 @@
 
 namespace mrt {
 
-constexpr uint32_t kNfDone = 0xFFFEu;     // Trav::sp: the near-first walk is over, its hit not yet checked
+constexpr uint32_t kNfDone = 0xFFFFu;     // Trav::sp: the near-first walk is over, its hit not yet checked
 constexpr uint32_t kNfRet = 0x80000000u;  // stack marker: leave the BLAS (back to the world ray)
+// Trav::sp: everything but the wild instances' tree is walked; the lane waits
+// (holding an END record, as a lane whose walk is over) until k_trace sends a
+// batch of such lanes into that tree together (nf_resume_wild)
+constexpr uint32_t kNfWait = 0xFFFEu;
+// the lane is not stepping: it waits for the wild tree's batch or for its hit's
+// check (the two largest values of sp: one compare beside every fetch)
+// (WILD false: no lane ever waits, and this is `sp == kNfDone`)
+template <bool WILD>
+MRT_HD bool nf_parked(const Trav& t) { return WILD ? t.sp >= kNfWait : t.sp == kNfDone; }
 
-struct NfStack {
-  uint32_t* p;  // this lane's entry 0 (LDS)
-  uint32_t stride;
-};
-MRT_HD void nf_push(const NfStack& k, Trav& t, uint32_t v) {
-  k.p[t.sp * k.stride] = v;
-  t.sp += 1;  // the builder bounds the depth (nf_stack_need <= kNfStack)
-}
+// (NfStack and nf_push are beside the walk's start in walk.h, which pushes
+// the wild instances' tree before anything else)
 // next record from the stack; false: the walk is over. A return marker
 // (leaving a BLAS) sits above world entries only — instances are world
 // objects, never nested — so one pop meets at most one: straight-line code,
 // the marker's branch taken only by the lanes that leave a BLAS.
+template <bool WILD>
 MRT_HD bool nf_pop(const TravIn& in, const NfStack& k, Trav& t) {
   if (t.sp == 0) return false;
   t.sp -= 1;
   t.nl = INFINITY;  // a popped node's exit is not kept (LDS: the stack's words are the walk's occupancy limit)
   uint32_t v = k.p[t.sp * k.stride];
-  if (v == kNfRet) {
-    const bool inst = (t.ret & kRetInstance) != 0;
-    t.ret = kNoRet;
-    if (inst) {  // a model shares the world ray (and its margin)
-      t.r = world_ray(in, t.ray);
-      nf_margin(in, t);
+  // a marker: kNfRet, or with WILD also kNfWildMark (both bit 31: one test on the common path)
+  if (WILD ? (int32_t)v < 0 : v == kNfRet) {
+    if (!WILD || v == kNfRet) {
+      const bool inst = (t.ret & kRetInstance) != 0;
+      t.ret = kNoRet;
+      if (inst) {  // a model shares the world ray (and its margin)
+        t.r = world_ray(in, t.ray);
+        nf_margin(in, t);
+      }
+      if (t.sp == 0) return false;
+      t.sp -= 1;
+      v = k.p[t.sp * k.stride];
     }
-    if (t.sp == 0) return false;
-    t.sp -= 1;
-    v = k.p[t.sp * k.stride];
+    if (WILD && v == kNfWildMark) {  // the bottom entry in a scene with a wild tree (walk.h nf_start)
+      t.sp = kNfWait;
+      t.s1.w = KIND_END;  // never a box (k_trace's box-run ballot)
+      return true;
+    }
   }
   t.i = v;
   return true;
+}
+// a waiting lane enters the wild instances' tree: the world ray and its margin
+// are in place (every BLAS was left), the stack is empty
+MRT_HD void nf_resume_wild(const TravIn& in, Trav& t) {
+  t.sp = 0;
+  t.i = in.S.nf_wild_root;  // the caller fetches it
 }
 MRT_HD uint32_t vnf_entry(const DevScene& S, uint32_t base, uint32_t id, uint32_t word) {
   return S.vnf_leaf[2 * (size_t)MRT_IDX(S, S.vnf_base[base] + id, S.n_vnf, 23) + word];
@@ -244,7 +262,7 @@ MRT_HD bool wave_any(bool p) {
 // The current record is an NF node: both children's boxes tested (culling at
 // best * (1 + 2^-10)); both hit: the nearer next, the other pushed; one: that
 // one; none: the stack's next.
-template <bool COUNT>
+template <bool COUNT, bool WILD>
 MRT_HD void trav_box_index_nf(const TravIn& in, const NfStack& k, Trav& t, LocalCounters& lc) {
   if (COUNT) lc.node_visits += 2;
   bool h[2];
@@ -273,7 +291,7 @@ MRT_HD void trav_box_index_nf(const TravIn& in, const NfStack& k, Trav& t, Local
   t.i = left ? base : right;
   t.nl = left ? x[0] : x[1];
   if (h[0] && h[1]) nf_push(k, t, left ? right : base);
-  if (!(h[0] || h[1]) && !nf_pop(in, k, t)) nf_over(t);
+  if (!(h[0] || h[1]) && !nf_pop<WILD>(in, k, t)) nf_over(t);
 }
 
 // A wild instance's leaf record (slot0.w: its WILD entry, layout.h): does the
@@ -288,7 +306,7 @@ MRT_HD bool nf_wild_enter(const TravIn& in, const Trav& t, uint32_t at) {
 }
 
 // The current record is an NF leaf's primitive, instance or model.
-template <bool COUNT, uint32_t ALPHA>
+template <bool COUNT, uint32_t ALPHA, bool WILD>
 MRT_HD void trav_prim_index_nf(const TravIn& in, const NfStack& k, Trav& t, LocalCounters& lc) {
   const DevScene& S = in.S;
   const uint4 s0 = t.s0, s1 = t.s1;
@@ -332,7 +350,7 @@ MRT_HD void trav_prim_index_nf(const TravIn& in, const NfStack& k, Trav& t, Loca
     return;
   }
   t.i = next;
-  if (next == kNfPop && !nf_pop(in, k, t)) nf_over(t);
+  if (next == kNfPop && !nf_pop<WILD>(in, k, t)) nf_over(t);
 }
 
 }  // namespace mrt

@@ -282,8 +282,9 @@ Hit walk_ref(const Scene& c, V o, V d, Stats* st = nullptr, bool check = false) 
 // The verified near-first walk in the per-lane order of k_trace's NF variant:
 // the reference's steps once it has fallen back, the winner's check when the
 // walk is over, else a near-first step.
-template <uint32_t ALPHA>
-Hit walk_nf(const Scene& c, V o, V d, Stats& st, uint64_t& fallbacks, uint64_t& starts_ref) {
+// WILD: the scene has a wild tree (k_trace's variant for it, trace.hip launch_trace)
+template <uint32_t ALPHA, bool WILD>
+Hit walk_nf_w(const Scene& c, V o, V d, Stats& st, uint64_t& fallbacks, uint64_t& starts_ref) {
   OneRay p(c.S, o, d);
   const TravIn& in = p.in;
   // two words beyond kNfStack: a step pushes at most two, so an overflow is
@@ -292,11 +293,16 @@ Hit walk_nf(const Scene& c, V o, V d, Stats& st, uint64_t& fallbacks, uint64_t& 
   const NfStack stk{words, 1};
   Trav t;
   LocalCounters lc;
-  trav_init(in, t, 0, INFINITY, c.S.nf_world);
+  trav_init_nf<WILD>(in, stk, t, 0, INFINITY, c.S.nf_world);  // as k_trace: with a wild tree its marker goes to the stack first
   if (t.sp == kExactMode) ++starts_ref;  // nf_start: the bound does not cover this ray
   while (!t.done) {
     if (t.sp == kExactMode) {
       ref_step<ALPHA>(c, in, t, lc, &st, false, o, d);
+      continue;
+    }
+    if (WILD && t.sp == kNfWait) {  // k_trace sends a batch of such lanes into the wild tree; one lane is its own batch
+      nf_resume_wild(in, t);
+      trav_fetch(in, t);
       continue;
     }
     if (t.sp == kNfDone) {
@@ -309,7 +315,7 @@ Hit walk_nf(const Scene& c, V o, V d, Stats& st, uint64_t& fallbacks, uint64_t& 
     const bool in_inst = t.ret != kNoRet && (t.ret & kRetInstance);
     if (trav_at_box(t)) {
       st.loads += 2;
-      trav_box_index_nf<true>(in, stk, t, lc);
+      trav_box_index_nf<true, WILD>(in, stk, t, lc);
     } else {
       const uint32_t kind = t.s1.w;
       if (kind == KIND_TRI || kind == KIND_SPHERE) {
@@ -324,18 +330,24 @@ Hit walk_nf(const Scene& c, V o, V d, Stats& st, uint64_t& fallbacks, uint64_t& 
         fprintf(stderr, "nf: unsupported kind %u at %u\n", kind, t.i);
         exit(2);
       }
-      trav_prim_index_nf<true, ALPHA>(in, stk, t, lc);
+      trav_prim_index_nf<true, ALPHA, WILD>(in, stk, t, lc);
     }
     if (in_inst && t.ret == kNoRet) st.loads += 2;  // the step left an instance: the world ray again
-    if (t.sp != kNfDone && t.sp > kNfStack) {
+    if (!nf_parked<WILD>(t) && t.sp > kNfStack - (WILD ? 0u : 1u)) {  // k_trace's LDS words per lane (launch_trace)
       fprintf(stderr, "nf: stack overflow\n");
       exit(3);
     }
-    if (t.sp != kNfDone) trav_fetch(in, t);
+    if (!nf_parked<WILD>(t)) trav_fetch(in, t);
   }
   st.boxes += lc.node_visits;
   fallbacks += lc.vnf_fallbacks;
   return trav_hit(in, t);
+}
+
+template <uint32_t ALPHA>
+Hit walk_nf(const Scene& c, V o, V d, Stats& st, uint64_t& fallbacks, uint64_t& starts_ref) {
+  return c.S.nf_wild_root != 0 ? walk_nf_w<ALPHA, true>(c, o, d, st, fallbacks, starts_ref)
+                               : walk_nf_w<ALPHA, false>(c, o, d, st, fallbacks, starts_ref);
 }
 
 bool same_hit(const Hit& r, const Hit& q) {
@@ -421,6 +433,7 @@ int run(int argc, char** argv, const mrt_scene_desc& d, const mrt_camera& cam, H
     g_leaf_parent.assign(s.vnf_leaf.size() / 2, ~0u);
     std::vector<uint8_t> seen(s.slots.size() / 4, 0);
     map_nf_tree(s, s.nf_world, seen);
+    if (s.nf_wild_root) map_nf_tree(s, s.nf_wild_root, seen);  // the wild instances' own tree (layout.h)
     printf("%-14s nf cones: %u of %u nodes carry one, kc %.3g\n", argv[1], s.nf_cones, s.nf_boxes, (double)s.nfb.kc);
     for (const auto& [inst, at] : g_wild_entry) {
       const NfWild e = wild_entry(s, at);
