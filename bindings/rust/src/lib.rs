@@ -44,6 +44,9 @@ pub struct SceneSink {
     pub surfaces: Vec<mrt_surface>,
     pub textures: Vec<mrt_texture>,
     pub volumes: Vec<mrt_volume>,
+    /// Volume<Instance<_>> / Volume<Model<_>>: the boundary of each such volume
+    /// (mrt_upload_scene_targets); a Volume<Sphere> has no entry
+    pub volume_targets: Vec<mrt_volume_target>,
     /// EveMaterial records: an MRT_MAT_EVE material's `surface` indexes this table
     pub eve_materials: Vec<mrt_eve_material>,
     /// RGBA8 storage the `textures` entries point into (kept alive by the sink)
@@ -166,6 +169,13 @@ impl Context {
     pub fn upload_ext(&mut self, scene: &mrt_scene_desc, ext: &mrt_scene_ext, camera: &mrt_camera)
         -> Result<(), MrtError> {
         self.check(unsafe { mrt_upload_scene_ext(self.raw, scene, ext) })?;
+        self.check(unsafe { mrt_set_camera(self.raw, camera) })
+    }
+
+    /// `upload_ext` for a world that holds fog boxes (SceneSink::volume_targets).
+    pub fn upload_targets(&mut self, scene: &mrt_scene_desc, ext: &mrt_scene_ext, targets: &[mrt_volume_target],
+                          camera: &mrt_camera) -> Result<(), MrtError> {
+        self.check(unsafe { mrt_upload_scene_targets(self.raw, scene, ext, targets.as_ptr(), targets.len() as u32) })?;
         self.check(unsafe { mrt_set_camera(self.raw, camera) })
     }
 

@@ -187,6 +187,16 @@ pub struct mrt_volume {
     pub material: u32,
 }
 
+/// Volume<Instance<_>> / Volume<Model<_>>: volume `volume` has `target` =
+/// mrt_ref(MRT_REF_INSTANCE | MRT_REF_MODEL, index) as its boundary
+/// (mrt_upload_scene_targets).
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct mrt_volume_target {
+    pub volume: u32,
+    pub target: u32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct mrt_scene_desc {
@@ -383,6 +393,8 @@ extern "C" {
     pub fn mrt_abi_version() -> i32;
     pub fn mrt_upload_scene(ctx: *mut mrt_ctx, scene: *const mrt_scene_desc) -> i32;
     pub fn mrt_upload_scene_ext(ctx: *mut mrt_ctx, scene: *const mrt_scene_desc, ext: *const mrt_scene_ext) -> i32;
+    pub fn mrt_upload_scene_targets(ctx: *mut mrt_ctx, scene: *const mrt_scene_desc, ext: *const mrt_scene_ext,
+                                    targets: *const mrt_volume_target, n_targets: u32) -> i32;
     pub fn mrt_set_camera(ctx: *mut mrt_ctx, camera: *const mrt_camera) -> i32;
     pub fn mrt_shade_rays(ctx: *mut mrt_ctx, rays: *const f32, n: u32, t_min: f32, t_max: f32, seed: u64,
                           out: *mut mrt_shade_out) -> i32;
@@ -456,6 +468,11 @@ extern "C" {
     pub fn mrt_builder_eve_material(b: *mut mrt_builder, no_surface: u32, ar_surface: u32, pmdg_surface: u32,
                                     colors: *const f32, glow: *const f32) -> i32;
     pub fn mrt_builder_desc_ext(b: *mut mrt_builder, ext: *mut mrt_scene_ext) -> i32;
+    pub fn mrt_builder_add_volume_instance(b: *mut mrt_builder, model: i32, translation: *const f32,
+                                           rotation: *const f32, scale: *const f32, density: f32,
+                                           albedo: *const f32) -> i32;
+    pub fn mrt_builder_add_volume_model(b: *mut mrt_builder, model: i32, density: f32, albedo: *const f32) -> i32;
+    pub fn mrt_builder_volume_targets(b: *mut mrt_builder, targets: *mut *const mrt_volume_target, n: *mut u32) -> i32;
     pub fn mrt_builder_background(b: *mut mrt_builder, kind: u32, surface: u32, r: f32, g: f32, bl: f32) -> i32;
     pub fn mrt_builder_background_cubemap(b: *mut mrt_builder, faces: *const u32, rotation: *const f32) -> i32;
     pub fn mrt_builder_ycbcr(b: *mut mrt_builder, luma: u32, chroma: u32) -> i32;

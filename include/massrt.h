@@ -63,7 +63,8 @@ extern "C" {
 #define MRT_REF_TRIANGLE 3u /* Triangle           geom.rs:503-593 */
 #define MRT_REF_INSTANCE 4u /* Instance (of BLAS) geom.rs:403-425 */
 #define MRT_REF_MODEL 5u    /* Model (owns BLAS)  geom.rs:317-333 */
-#define MRT_REF_VOLUME 6u   /* Volume<Sphere>     geom.rs:594-660 (world level only) */
+#define MRT_REF_VOLUME 6u   /* Volume<I>          geom.rs:594-660 (world level only; I = Sphere, or the
+                               Instance / Model an mrt_volume_target names) */
 #define MRT_REF(kind, idx) ((((uint32_t)(kind)) << MRT_REF_KIND_SHIFT) | ((uint32_t)(idx)&MRT_REF_INDEX_MASK))
 #define MRT_REF_KIND(r) (((uint32_t)(r)) >> MRT_REF_KIND_SHIFT)
 #define MRT_REF_INDEX(r) (((uint32_t)(r)) & MRT_REF_INDEX_MASK)
@@ -164,7 +165,8 @@ typedef struct {
 } mrt_background;
 
 /* Volume::new(Sphere::new((), center, radius), density, albedo): a constant-
- * density medium in a sphere (the reference's only Volume target, eve.rs:41);
+ * density medium in a sphere (the Volume target of eve.rs:41; an instance or
+ * model as the boundary: mrt_volume_target below);
  * `material` is its Isotrophic(albedo) (material.rs:428-445). Its
  * intersection draws from the path RNG (geom.rs:640). */
 typedef struct {
@@ -216,6 +218,19 @@ typedef struct {
   const mrt_eve_material* eve_materials;
   uint32_t n_eve_materials;
 } mrt_scene_ext;
+
+/* Volume::new(model.instance(..), density, albedo) and Volume::new(model, ..)
+ * (Volume<I: Intersect> is generic over its boundary, geom.rs:595-660):
+ * volume `volume` of mrt_scene_desc.volumes has `target` =
+ * MRT_REF(MRT_REF_INSTANCE | MRT_REF_MODEL, index) as its boundary and ignores
+ * its own center and radius. The target lives in instances[] / models[] like
+ * any other and need not be referenced by the tree (the Volume owns it); its
+ * override material is never seen. Its BLAS may hold boxes and triangles
+ * only. Passed beside the description (mrt_upload_scene_targets). */
+typedef struct {
+  uint32_t volume;
+  uint32_t target;
+} mrt_volume_target;
 
 /* Camera fields precomputed by Camera::new (world.rs:5-51). */
 typedef struct {
@@ -331,6 +346,13 @@ int mrt_upload_scene(mrt_ctx* ctx, const mrt_scene_desc* scene);
  * NULL: exactly mrt_upload_scene). An MRT_MAT_EVE material whose index is not
  * in ext->eve_materials is MRT_ERR_INVALID. */
 int mrt_upload_scene_ext(mrt_ctx* ctx, const mrt_scene_desc* scene, const mrt_scene_ext* ext);
+/* mrt_upload_scene_ext with the volumes whose boundary is an instance or a
+ * model (ext may be NULL; n_targets == 0: exactly mrt_upload_scene_ext).
+ * MRT_ERR_INVALID: a volume or target index out of range, a target that is
+ * neither an instance nor a model, a volume listed twice, a target BLAS that
+ * holds anything but boxes and triangles. */
+int mrt_upload_scene_targets(mrt_ctx* ctx, const mrt_scene_desc* scene, const mrt_scene_ext* ext,
+                             const mrt_volume_target* targets, uint32_t n_targets);
 int mrt_set_camera(mrt_ctx* ctx, const mrt_camera* camera);
 /* host buffers: accum_rgb = width*height*3 floats, accum_bounces = width*height */
 int mrt_render(mrt_ctx* ctx, const mrt_render_args* args, float* accum_rgb, uint32_t* accum_bounces);
@@ -570,8 +592,8 @@ int mrt_builder_free(mrt_builder* b);
 const char* mrt_builder_last_error(void);
 /* Scene::generate of a built-in scene, then World::build_bvh (main.rs:107-112).
  * names: "sphere_grid", "cornell", "cube_field", "mesh_ply", "mesh_obj",
- *        "mesh_obj_textured", "menger", "menger_l3", "eve"; asset_dir holds
- *        cube.ply and generated assets. */
+ *        "mesh_obj_textured", "menger", "menger_l3", "eve", "cornell_smoke";
+ *        asset_dir holds cube.ply and generated assets. */
 int mrt_builder_builtin(mrt_builder* b, const char* name, float aspect_ratio, const char* asset_dir);
 float mrt_builder_rand_f32(mrt_builder* b); /* f32::rand() on the scene stream */
 /* surfaces / materials; each returns an index >= 0 */
@@ -582,6 +604,14 @@ int mrt_builder_material(mrt_builder* b, uint32_t kind, uint32_t surface, float 
 /* World::add(Volume::new(Sphere::new((), center, radius), density, albedo));
  * returns the volume index */
 int mrt_builder_add_volume(mrt_builder* b, const float* center, float radius, float density, const float* albedo);
+/* World::add(Volume::new(model.instance(translation, rotation, scale), density,
+ * albedo)) and World::add(Volume::new(model, density, albedo)): `model` is a
+ * handle of mrt_builder_model*; the volume's box is its target's
+ * (geom.rs:657-659). Each returns the volume index; the target goes into the
+ * table of mrt_builder_volume_targets. */
+int mrt_builder_add_volume_instance(mrt_builder* b, int model, const float* translation, const float* rotation,
+                                    const float* scale, float density, const float* albedo);
+int mrt_builder_add_volume_model(mrt_builder* b, int model, float density, const float* albedo);
 /* EveMaterial::new(no, ar, pmdg, colors) (eve.rs:44-64): three surfaces of kind
  * MRT_SURF_TEXTURE (else -MRT_ERR_INVALID), colors = EveMaterialColor::colors
  * (12 floats), glow (3 floats); returns the material index */
@@ -631,6 +661,9 @@ int mrt_builder_last_build_ms(mrt_builder* b, double* host_ms, double* device_ms
 int mrt_builder_desc(mrt_builder* b, mrt_scene_desc* desc, mrt_camera* camera);
 /* the tables beside the description (mrt_upload_scene_ext); pointers valid as for mrt_builder_desc */
 int mrt_builder_desc_ext(mrt_builder* b, mrt_scene_ext* ext);
+/* the volume targets beside the description (mrt_upload_scene_targets): *targets points at *n entries
+ * (NULL and 0 for a world without such volumes); valid as for mrt_builder_desc */
+int mrt_builder_volume_targets(mrt_builder* b, const mrt_volume_target** targets, uint32_t* n);
 
 /* ---- display / export (main.rs:640-722, 760-783) ----------------------- */
 /* Image::to_rgb_bytes + dump's row flip: accumulated colour sums (W*H*3

@@ -170,7 +170,12 @@ int mrt_destroy(mrt_ctx* c) {
 int mrt_upload_scene(mrt_ctx* c, const mrt_scene_desc* d) { return mrt_upload_scene_ext(c, d, nullptr); }
 
 int mrt_upload_scene_ext(mrt_ctx* c, const mrt_scene_desc* d, const mrt_scene_ext* ext) {
-  MRT_EACH(c, mrt_upload_scene_ext(c, d, ext));
+  return mrt_upload_scene_targets(c, d, ext, nullptr, 0);
+}
+
+int mrt_upload_scene_targets(mrt_ctx* c, const mrt_scene_desc* d, const mrt_scene_ext* ext,
+                             const mrt_volume_target* targets, uint32_t n_targets) {
+  MRT_EACH(c, mrt_upload_scene_targets(c, d, ext, targets, n_targets));
   return guarded(c, [&] {
     if (!d) throw ApiError{MRT_ERR_INVALID, "null scene"};
     HostScene hs;
@@ -178,7 +183,7 @@ int mrt_upload_scene_ext(mrt_ctx* c, const mrt_scene_desc* d, const mrt_scene_ex
     // NF trees per the option in effect at upload (upload.h nf_build)
     hs.nf_build = c->opt[OPT_TRAVERSAL] == MRT_TRAVERSAL_REFERENCE ? kNfBuildNever
                   : c->opt[OPT_TRAVERSAL] == MRT_TRAVERSAL_NEAR_FIRST ? kNfBuildAlways : kNfBuildAuto;
-    if (!build_host_scene(*d, hs, err, true, ext)) throw ApiError{MRT_ERR_INVALID, err};
+    if (!build_host_scene(*d, hs, err, true, ext, targets, n_targets)) throw ApiError{MRT_ERR_INVALID, err};
     build_treelet(hs, (uint32_t)((size_t)c->tun.treelet_kb * 1024 / 16));
     // one allocation, 256-B aligned sections
     size_t off = 0;
@@ -266,6 +271,7 @@ int mrt_upload_scene_ext(mrt_ctx* c, const mrt_scene_desc* d, const mrt_scene_ex
     c->facts.treelet = S.n_tlet > 0;
     c->facts.trav_rng = hs.trav_rng;
     c->scene_alpha = hs.has_alpha;
+    c->scene_vblas = hs.vol_blas;
     c->scene_ext = !hs.surf_ops.empty() || hs.bg_kind == MRT_BG_CUBEMAP || !hs.eve.empty();
     apply_options(c);  // the per-scene rules of the options left at -1
     c->has_scene = true;

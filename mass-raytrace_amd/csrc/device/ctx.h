@@ -66,6 +66,7 @@ struct mrt_ctx {
   mrt::SceneFacts facts;
   mrt::Tuning tun{};
   bool scene_alpha = true;  // the scene has alpha-tested triangles
+  bool scene_vblas = false;  // a volume whose target is an instance or a model (k_trace's VBLAS variants)
   bool scene_ext = false;   // composite surfaces, a CubeMap background or Eve materials (the EXT kernel variants)
   // render state
   size_t pool_cap = 0;  // paths over all queues

@@ -25,6 +25,10 @@
 //   INST   2 slots  {inst_id,blas_begin,blas_end,0} {0,0,0,INST}
 //   MODEL  2 slots  {model_id,blas_begin,blas_end,0} {0,0,0,MODEL}
 //   VOLUME 2 slots  {cx,cy,cz,r}              {volume_id,next,0,VOLUME}  (sphere target)
+//   VOLUME 2 slots  {blas_begin,target_id,0,0} {volume_id,next,kVolInstance|kVolModel,VOLUME}
+//          (instance or model target: two closest-hit searches of the shared
+//          BLAS region from inside the walk, walk.h volume_hit_blas; that
+//          region holds boxes and triangles only)
 //   END    2 slots  {0,0,0,0}                 {0,0,0,END}   closes every region
 // Slots between records (alignment padding) are zero and never reached.
 // ab = b - a and ac = c - a are precomputed on the host with the same IEEE
@@ -38,6 +42,8 @@ namespace mrt {
 
 enum : uint32_t { KIND_BOX = 1, KIND_SPHERE = 2, KIND_TRI = 3, KIND_INST = 4, KIND_MODEL = 5, KIND_VOLUME = 6 };
 constexpr uint32_t kBoxFlag = 0x80000000u;  // slot1.w of a box: kBoxFlag | hit index
+// a VOLUME record's slot1.z: 0 = a sphere target, else its target is a BLAS
+enum : uint32_t { kVolInstance = 1, kVolModel = 2 };
 // LDS treelet (upload.cpp build_treelet): the most visited records are copied
 // into every k_trace workgroup's LDS. An index with kLdsTag names slot
 // (index & kIdxMask) of that copy; box hit/skip indices and instance/model

@@ -32,11 +32,12 @@ constexpr uint32_t kStashQuads = 4;  // float4s per lane of the world-ray stash 
 // near child first with a per-lane stack in LDS (kNfStack x BLK words of
 // dynamic shared memory), the winner checked against the reference tree,
 // rays that fail the check walked again the reference's way.
-template <bool COUNT, bool LDS, uint32_t ALPHA, bool RNG, int BLK, bool NF = false, bool WILD = false>
+template <bool COUNT, bool LDS, uint32_t ALPHA, bool RNG, int BLK, bool NF = false, bool WILD = false, bool VBLAS = false>
 __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(NF ? (COUNT ? 1 : 5) : (ALPHA == 0 && !RNG && !COUNT ? 8 : 1)))) void k_trace(DevScene S, PathBufs in, uint4* hits, Ctrl* ctrl, uint32_t cur,
                                                   DevCounters* cnt, float tmin, float tmax, TraceTune tune) {
   static_assert(!NF || (!LDS && !RNG), "the near-first walk has no treelet and no traversal draws");
   static_assert(!WILD || NF, "only the near-first walk has a wild tree");
+  static_assert(!VBLAS || RNG, "a volume draws");
   constexpr int R = 1;
   const uint32_t n = ctrl->active[cur];
   if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -178,7 +179,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(NF ? (COUNT
           if (NF && t[q].sp != kExactMode)
             trav_prim_index_nf<COUNT, ALPHA, WILD>(tin, stk, t[q], lc);
           else
-            trav_prim_index<COUNT, ALPHA, RNG, LDS>(tin, t[q], lc);
+            trav_prim_index<COUNT, ALPHA, RNG, LDS, VBLAS>(tin, t[q], lc);
         }
         if ((box_go || prim_go) && !t[q].done && (!NF || !nf_parked<WILD>(t[q]))) trav_fetch<LDS>(tin, t[q]);
         if (COUNT) {
@@ -296,25 +297,33 @@ __global__ __launch_bounds__(kBlock) void k_rays_out(DevScene S, PathBufs in, co
 // none / plain surfaces / composite surfaces (EXT); traversal draws; or the
 // near-first walk (scenes with NF trees, no treelet, no traversal draws).
 using TraceFn = void (*)(DevScene, PathBufs, uint4*, Ctrl*, uint32_t, DevCounters*, float, float, TraceTune);
-template <bool COUNT, uint32_t ALPHA, bool RNG>
+// RNG: 0 no traversal draws, 1 draws, 2 draws and volumes whose target is a
+// BLAS (VBLAS: the nested searches of walk.h volume_hit_blas cost registers,
+// so scenes without such a volume keep the kernels they had)
+template <bool COUNT, uint32_t ALPHA, uint32_t RNG>
 TraceFn trace_kernel_lds(int block) {
-  return block == 1024  ? k_trace<COUNT, true, ALPHA, RNG, 1024>
-         : block == 512 ? k_trace<COUNT, true, ALPHA, RNG, 512>
-                        : k_trace<COUNT, true, ALPHA, RNG, kBlock>;
+  return block == 1024  ? k_trace<COUNT, true, ALPHA, RNG != 0, 1024, false, false, RNG == 2>
+         : block == 512 ? k_trace<COUNT, true, ALPHA, RNG != 0, 512, false, false, RNG == 2>
+                        : k_trace<COUNT, true, ALPHA, RNG != 0, kBlock, false, false, RNG == 2>;
 }
 template <bool COUNT, uint32_t ALPHA>
-TraceFn trace_kernel_a(bool lds, bool rng, int block, bool nf, bool wild) {
+TraceFn trace_kernel_a(bool lds, uint32_t rng, int block, bool nf, bool wild) {
   if (nf) return wild ? k_trace<COUNT, false, ALPHA, false, kBlock, true, true> : k_trace<COUNT, false, ALPHA, false, kBlock, true, false>;
-  if (lds) return rng ? trace_kernel_lds<COUNT, ALPHA, true>(block) : trace_kernel_lds<COUNT, ALPHA, false>(block);
-  return rng ? k_trace<COUNT, false, ALPHA, true, kBlock> : k_trace<COUNT, false, ALPHA, false, kBlock>;
+  if (lds)
+    return rng == 2   ? trace_kernel_lds<COUNT, ALPHA, 2>(block)
+           : rng == 1 ? trace_kernel_lds<COUNT, ALPHA, 1>(block)
+                      : trace_kernel_lds<COUNT, ALPHA, 0>(block);
+  return rng == 2   ? k_trace<COUNT, false, ALPHA, true, kBlock, false, false, true>
+         : rng == 1 ? k_trace<COUNT, false, ALPHA, true, kBlock>
+                    : k_trace<COUNT, false, ALPHA, false, kBlock>;
 }
 template <bool COUNT>
-TraceFn trace_kernel_c(bool lds, uint32_t alpha, bool rng, int block, bool nf, bool wild) {
+TraceFn trace_kernel_c(bool lds, uint32_t alpha, uint32_t rng, int block, bool nf, bool wild) {
   return alpha == 2   ? trace_kernel_a<COUNT, 2>(lds, rng, block, nf, wild)
          : alpha == 1 ? trace_kernel_a<COUNT, 1>(lds, rng, block, nf, wild)
                       : trace_kernel_a<COUNT, 0>(lds, rng, block, nf, wild);
 }
-TraceFn trace_kernel(bool count, bool lds, uint32_t alpha, bool rng, int block, bool nf, bool wild) {
+TraceFn trace_kernel(bool count, bool lds, uint32_t alpha, uint32_t rng, int block, bool nf, bool wild) {
   return count ? trace_kernel_c<true>(lds, alpha, rng, block, nf, wild) : trace_kernel_c<false>(lds, alpha, rng, block, nf, wild);
 }
 
@@ -350,7 +359,8 @@ void launch_trace(mrt_ctx* c, hipStream_t st, const Queue& q, const PathBufs& in
   // a scene with a wild tree (layout.h nf_wild_root) runs the variant that walks it last, in batches; the
   // others compile none of that and keep 24 stack words (the builder leaves them the marker's word unused)
   const bool wild = nf && c->S.nf_wild_root != 0;
-  const TraceFn f = trace_kernel(count, lds, alpha, c->facts.trav_rng, block, nf, wild);
+  const uint32_t rng = c->facts.trav_rng ? (c->scene_vblas ? 2u : 1u) : 0u;
+  const TraceFn f = trace_kernel(count, lds, alpha, rng, block, nf, wild);
   // dynamic LDS: the near-first stack (kNfStack words per lane), the treelet, or the world-ray stash (4 x 16 B per lane)
   const size_t smem = nf ? (size_t)(kNfStack - (wild ? 0u : 1u)) * block * 4 : lds ? (size_t)c->S.n_tlet * 16 : (size_t)kStashQuads * block * 16;
   // Near-first: 24 KiB of LDS per workgroup of 256 lanes, kNfStack (25) with a

@@ -194,11 +194,22 @@ struct Emitter {
       case MRT_REF_VOLUME: {
         if (idx >= d.n_volumes) return fail("volume index out of range");
         if (in_blas) return fail("a Volume must be a World object (not inside a model)");
+        s.n_prim_records++;
+        s.trav_rng = true;
+        if (const uint32_t tr = vol_target[idx]) {  // Volume<Instance> / Volume<Model>: the target's shared BLAS
+          const bool inst = MRT_REF_KIND(tr) == MRT_REF_INSTANCE;
+          const uint32_t ti = MRT_REF_INDEX(tr);
+          const uint32_t root = inst ? d.instances[ti].blas_root : d.models[ti].blas_root;
+          if (root >= d.n_nodes) return fail("BLAS root out of range");
+          const uint32_t at = push_slot(0, ti, 0, 0);
+          push_slot(idx, at + 2, inst ? kVolInstance : kVolModel, KIND_VOLUME);
+          volume_patches.push_back({at, root});
+          s.vol_blas = true;
+          return true;
+        }
         const mrt_volume& v = d.volumes[idx];
         const uint32_t at = push_slot(fbits(v.center[0]), fbits(v.center[1]), fbits(v.center[2]), fbits(v.radius));
         push_slot(idx, at + 2, 0, KIND_VOLUME);
-        s.n_prim_records++;
-        s.trav_rng = true;
         return true;
       }
       case MRT_REF_INSTANCE:
@@ -228,6 +239,10 @@ struct Emitter {
   // the triangle's own material's surface can have a zero alpha.
   SurfResolver* surfaces = nullptr;
   bool mix_alpha = false;              // a uv triangle's alpha test draws random numbers
+  // jump_patches' twin for volume records whose target is an instance or a
+  // model, and each volume's target (mrt_volume_target; 0: its own sphere)
+  std::vector<std::pair<uint32_t, uint32_t>> volume_patches;
+  std::vector<uint32_t> vol_target;
   bool needs_alpha(const mrt_triangle& t) {
     if (!(t.flags & MRT_TRI_HAS_UV) || t.material >= d.n_materials) return false;
     const mrt_material& m = d.materials[t.material];
@@ -415,6 +430,9 @@ void relayout(HostScene& s) {
       rec[1] = remap[rec[1]];
       rec[2] = remap[rec[2]];
       if (remap[i + 2] != remap[i] + 2) throw std::logic_error("relayout: an instance moved away from its successor");
+    } else if (k == KIND_VOLUME && w[4 * (i + 1) + 2]) {  // its target's BLAS
+      uint32_t* rec = &out[4 * (size_t)remap[i]];
+      rec[0] = remap[rec[0]];
     }
   }
   s.world_begin = remap[s.world_begin];
@@ -434,7 +452,7 @@ void put_m4_12(std::vector<float>& dst, const float* m16) {
 }  // namespace
 
 bool build_host_scene(const mrt_scene_desc& d, HostScene& s, std::string& err, bool sibling_layout,
-                      const mrt_scene_ext* ext) {
+                      const mrt_scene_ext* ext, const mrt_volume_target* targets, uint32_t n_targets) {
   const bool keep = s.keep_nf_boxes;
   const int nf_build = s.nf_build;
   s = HostScene{};
@@ -442,6 +460,19 @@ bool build_host_scene(const mrt_scene_desc& d, HostScene& s, std::string& err, b
   s.nf_build = nf_build;
   SurfResolver surf{d, s, err, {}, {}};
   Emitter e{d, s, err, {}, &surf};
+  // volumes whose boundary is an instance or a model (mrt_volume_target)
+  e.vol_target.assign(d.n_volumes, 0u);
+  if (n_targets && !targets) return (err = "null volume target table", false);
+  for (uint32_t i = 0; i < n_targets; ++i) {
+    const uint32_t v = targets[i].volume, tk = MRT_REF_KIND(targets[i].target), ti = MRT_REF_INDEX(targets[i].target);
+    if (v >= d.n_volumes) return (err = "volume target: volume index out of range", false);
+    if (tk != MRT_REF_INSTANCE && tk != MRT_REF_MODEL)
+      return (err = "volume target: the target must be an instance or a model", false);
+    if (ti >= (tk == MRT_REF_INSTANCE ? d.n_instances : d.n_models))
+      return (err = "volume target: target index out of range", false);
+    if (e.vol_target[v]) return (err = "volume target: a volume listed twice", false);
+    e.vol_target[v] = targets[i].target;
+  }
   // materials
   for (uint32_t i = 0; i < d.n_materials; ++i) {
     const mrt_material& m = d.materials[i];
@@ -603,6 +634,27 @@ bool build_host_scene(const mrt_scene_desc& d, HostScene& s, std::string& err, b
     s.slots[4 * p.first + 1] = r.begin;
     s.slots[4 * p.first + 2] = r.end;
   }
+  // the targets of volumes: the same regions, shared with the instances and
+  // models of the same BLAS. The nested searches (walk.h volume_hit_blas) step
+  // boxes and triangles and end on the END record: nothing else may be there.
+  for (auto& p : e.volume_patches) {
+    auto it = blas.find(p.second);
+    if (it == blas.end()) {
+      uint32_t b = e.n_slots();
+      if (!e.emit_tree(MRT_REF(MRT_REF_NODE, p.second), true)) return false;
+      s.blas_regions.push_back({b, e.n_slots(), 0, false});
+      it = blas.emplace(p.second, s.blas_regions.size() - 1).first;
+      e.push_end();
+    }
+    BlasRegion& r = s.blas_regions[it->second];
+    for (auto rs = std::lower_bound(s.rec_starts.begin(), s.rec_starts.end(), r.begin);
+         rs != s.rec_starts.end() && *rs < r.end; ++rs)
+      if (!rec_is_box(s.slots, *rs) && rec_kind(s.slots, *rs) != KIND_TRI)
+        return (err = "a volume target's BLAS must hold triangles only", false);
+    r.refs++;
+    if (s.slots[4 * (p.first + 1) + 2] == kVolModel) r.model = true;
+    s.slots[4 * p.first] = r.begin;
+  }
   if (e.mix_alpha) s.trav_rng = true;
   if (sibling_layout) relayout(s);  // false: the plain preorder stream (tools/slab_check.cpp layout check)
   if (!build_nf_trees(d, s, err)) return false;  // appended after the reference stream (layout.h)
@@ -710,6 +762,7 @@ void build_treelet(HostScene& s, uint32_t budget) {
       rec[11] = R(rec[11]);
     } else if (rec[7] == KIND_SPHERE || rec[7] == KIND_VOLUME) {
       rec[5] = R(rec[5]);
+      if (rec[7] == KIND_VOLUME && rec[6]) rec[0] = R(rec[0]);  // its target's BLAS
     }
   };
   s.slots_tl = w;

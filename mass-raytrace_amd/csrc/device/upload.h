@@ -32,6 +32,7 @@ struct HostScene {
   uint32_t early_ok = 1;  // every box coordinate finite and within 2^28: the early slab decision applies
   bool has_alpha = false;  // some triangle carries TRI_FLAG_ALPHA
   bool trav_rng = false;   // the traversal draws random numbers (Volume, Mix alpha tests)
+  bool vol_blas = false;   // some volume's target is an instance or a model (walk.h volume_hit_blas)
   std::vector<float> vol_nid;
   std::vector<uint32_t> vol_mat;
   // Volume draws f = m * 2^-23 (m < 2^23, mrt_rng.h) and takes f.ln()
@@ -136,8 +137,11 @@ bool build_nf_trees(const mrt_scene_desc& d, HostScene& s, std::string& err);
 // sibling_layout=false keeps every region in plain preorder (the layout
 // before round 2; tools/slab_check.cpp runs the walk over both: they walk alike)
 // ext: the tables beside the description (mrt_upload_scene_ext); null: none.
+// targets: the volumes whose boundary is an instance or a model
+// (mrt_upload_scene_targets).
 bool build_host_scene(const mrt_scene_desc& d, HostScene& out, std::string& err, bool sibling_layout = true,
-                      const mrt_scene_ext* ext = nullptr);
+                      const mrt_scene_ext* ext = nullptr, const mrt_volume_target* targets = nullptr,
+                      uint32_t n_targets = 0);
 
 // Chooses the records copied into LDS by every k_trace workgroup (at most
 // `budget` 16-byte slots): the whole stream when it fits; else the small BLAS

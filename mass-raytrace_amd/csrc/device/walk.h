@@ -278,16 +278,13 @@ MRT_HD void trav_store_rng(const TravIn& in, const Trav& t) {
                              (uint32_t)(t.rng.s1 >> 32));
 }
 
-// Volume::intersect with a sphere target (geom.rs:609-653): entry and exit of
-// the target over the whole line, clipped to [tmin, best], then a distance
-// f.ln() * -1/density drawn from the ray's stream; the ln is looked up
-// (S.ln_table, upload.h) for the exact value of the host libm.
-MRT_HD bool volume_hit(const DevScene& S, const TravIn& in, Trav& t, uint4 s0, uint32_t vid, float& th) {
-  const V3 c{u2f(s0.x), u2f(s0.y), u2f(s0.z)};
-  const float rad = u2f(s0.w);
-  float te, tx;
-  if (!sphere_hit(c, rad, t.r.o, t.r.d, t.r.a, -INFINITY, INFINITY, te)) return false;
-  if (!sphere_hit(c, rad, t.r.o, t.r.d, t.r.a, te + 0.0001f, INFINITY, tx)) return false;
+// Volume::intersect once entry and exit of the target over the whole line are
+// known (geom.rs:623-653): both clipped to [tmin, best], then a distance
+// f.ln() * -1/density drawn from the ray's stream — after every early return,
+// as there; the ln is looked up (S.ln_table, upload.h) for the exact value of
+// the host libm. t.r is the world ray: its length scales the distance, also
+// for an instance target (t is shared between the two spaces).
+MRT_HD bool volume_scatter(const DevScene& S, const TravIn& in, Trav& t, uint32_t vid, float te, float tx, float& th) {
   if (te < in.tmin) te = in.tmin;
   if (tx > t.best) tx = t.best;
   if (te >= tx) return false;
@@ -301,13 +298,112 @@ MRT_HD bool volume_hit(const DevScene& S, const TravIn& in, Trav& t, uint4 s0, u
   return true;
 }
 
-// The current record is a primitive, an instance or a model.
+// Volume::intersect with a sphere target (geom.rs:609-622): entry and exit of
+// the target over the whole line.
+MRT_HD bool volume_hit(const DevScene& S, const TravIn& in, Trav& t, uint4 s0, uint32_t vid, float& th) {
+  const V3 c{u2f(s0.x), u2f(s0.y), u2f(s0.z)};
+  const float rad = u2f(s0.w);
+  float te, tx;
+  if (!sphere_hit(c, rad, t.r.o, t.r.d, t.r.a, -INFINITY, INFINITY, te)) return false;
+  if (!sphere_hit(c, rad, t.r.o, t.r.d, t.r.a, te + 0.0001f, INFINITY, tx)) return false;
+  return volume_scatter(S, in, t, vid, te, tx, th);
+}
+
+// The current record is a triangle: Triangle::intersect against [in.tmin,
+// t.best], then on to the record after it.
 // ALPHA: 0 no alpha tests (the specialisation for scenes without alpha-tested
 // triangles: the alpha test's registers would otherwise cost occupancy
 // everywhere), 1 alpha tests, 2 alpha tests over EXT surfaces.
+template <bool COUNT, uint32_t ALPHA, bool RNG, bool LDS>
+MRT_HD void trav_tri_index(const TravIn& in, Trav& t, LocalCounters& lc, uint4 s0, uint4 s1) {
+  if (COUNT) lc.triangle_tests++;
+  const uint4 s2 = rec_load1<LDS>(in, t.i + 2);
+  V3 a{u2f(s0.x), u2f(s0.y), u2f(s0.z)}, ab{u2f(s0.w), u2f(s1.x), u2f(s1.y)}, ac{u2f(s2.x), u2f(s2.y), u2f(s2.z)};
+  float th;
+  if (tri_hit(a, ab, ac, t.r.o, t.r.d, in.tmin, t.best, th)) {
+    const uint32_t id = s1.z & kTriIdMask;
+    if (!ALPHA || !(s1.z & kTriAlpha) || tri_alpha_pass<RNG, ALPHA == 2>(in.S, id, t.r.o, t.r.d, th, t.rng, lc)) {
+      t.best = th;
+      t.prim = make_ref(MRT_REF_TRIANGLE, id);
+      t.hit_ret = t.ret;
+    }
+  }
+  t.i = s2.w;
+}
+
+// Volume::intersect with an instance or a model as the target (geom.rs:609-
+// 622 over Instance::intersect / Model::intersect, 317-328 and 403-420): two
+// closest-hit searches of the target's BLAS region, BvhNode::intersect(ray,
+// -inf, +inf) and then (ray, enter + 0.0001, +inf); alpha tests of its
+// triangles draw from the ray's stream in traversal order, before the
+// volume's own draw. The lane that met the record runs both with its own
+// Trav, in ONE loop (the second search restarts it: the box and triangle
+// steps are inlined once), so nothing but the few words saved here is live
+// across them: an instance target's object-space ray replaces t.r (the world
+// ray comes back the way leaving an instance brings it back,
+// trav_end_index), and best, prim and hit_ret are put back; t.ret stays
+// kNoRet throughout (volumes are world objects), t.rng advances by the draws
+// made, and t.i / t.s0 / t.s1 are the caller's to set (it holds the record's
+// copy). The region holds boxes and triangles and ends in its END record
+// (upload.cpp checks that): any other record ends a search, so no stream can
+// spin the loop. Counters: what the reference executes — every box and
+// triangle test of both searches, one instance / model entry per search.
+template <bool COUNT, uint32_t ALPHA, bool LDS>
+MRT_HD bool volume_hit_blas(const DevScene& S, const TravIn& in, Trav& t, LocalCounters& lc, uint4 s0, uint4 s1,
+                            float& th) {
+  const bool inst = s1.z == kVolInstance;
+  const float best = t.best;
+  const uint32_t prim = t.prim, hit_ret = t.hit_ret;
+  if (inst) {
+    V3 c0, c1, c2, c3;
+    load_m12(S.inst_inv + (size_t)MRT_IDX(S, s0.y, S.n_inst, 8) * 12, c0, c1, c2, c3);
+    if (in.stash) tray_stash(in, t.r);
+    t.r = make_tray(xform(c0, c1, c2, c3, t.r.o, 1.0f), xform(c0, c1, c2, c3, t.r.d, 0.0f), S.fast_ok);
+  }
+  TravIn vin = in;
+  vin.tmin = -INFINITY;
+  float te = 0.0f;
+  bool second = false, hit = false;
+  if (COUNT) (inst ? lc.instance_entries : lc.model_entries)++;
+  t.i = s0.x;
+  t.best = INFINITY;
+  t.prim = kRefNone;
+  for (;;) {
+    trav_fetch<LDS>(vin, t);
+    if (t.done) break;  // MRT_DEBUG_BOUNDS builds: the step cap
+    if (trav_at_box(t)) {
+      trav_box_index<COUNT>(vin, t, lc);
+    } else if (t.s1.w == KIND_TRI) {
+      trav_tri_index<COUNT, ALPHA, true, LDS>(vin, t, lc, t.s0, t.s1);
+    } else {  // the search is over
+      if (t.prim == kRefNone) break;  // enter or exit is None
+      hit = second;
+      if (second) break;
+      second = true;
+      te = t.best;
+      vin.tmin = te + 0.0001f;
+      if (COUNT) (inst ? lc.instance_entries : lc.model_entries)++;
+      t.i = s0.x;
+      t.best = INFINITY;
+      t.prim = kRefNone;
+    }
+  }
+  const float tx = t.best;
+  if (inst) t.r = in.stash ? tray_unstash(in) : world_ray(in, t.ray);
+  t.best = best;
+  t.prim = prim;
+  t.hit_ret = hit_ret;
+  t.done = false;
+  return hit && volume_scatter(S, in, t, s1.x, te, tx, th);
+}
+
+// The current record is a primitive, an instance or a model (ALPHA: as for
+// trav_tri_index).
 // trav_prim_index moves to the next record (or finishes the ray) without
 // loading it; trav_prim also loads it.
-template <bool COUNT, uint32_t ALPHA, bool RNG = false, bool LDS = false>
+// VBLAS: the scene may hold volumes whose target is a BLAS (only k_trace tells
+// the two apart: the nested searches cost it registers, trace.hip).
+template <bool COUNT, uint32_t ALPHA, bool RNG = false, bool LDS = false, bool VBLAS = RNG>
 MRT_HD void trav_prim_index(const TravIn& in, Trav& t, LocalCounters& lc) {
   const DevScene& S = in.S;
   const uint4 s0 = t.s0, s1 = t.s1;
@@ -317,19 +413,7 @@ MRT_HD void trav_prim_index(const TravIn& in, Trav& t, LocalCounters& lc) {
     return;
   }
   if (kind == KIND_TRI) {
-    if (COUNT) lc.triangle_tests++;
-    const uint4 s2 = rec_load1<LDS>(in, t.i + 2);
-    V3 a{u2f(s0.x), u2f(s0.y), u2f(s0.z)}, ab{u2f(s0.w), u2f(s1.x), u2f(s1.y)}, ac{u2f(s2.x), u2f(s2.y), u2f(s2.z)};
-    float th;
-    if (tri_hit(a, ab, ac, t.r.o, t.r.d, in.tmin, t.best, th)) {
-      const uint32_t id = s1.z & kTriIdMask;
-      if (!ALPHA || !(s1.z & kTriAlpha) || tri_alpha_pass<RNG, ALPHA == 2>(S, id, t.r.o, t.r.d, th, t.rng, lc)) {
-        t.best = th;
-        t.prim = make_ref(MRT_REF_TRIANGLE, id);
-        t.hit_ret = t.ret;
-      }
-    }
-    t.i = s2.w;
+    trav_tri_index<COUNT, ALPHA, RNG, LDS>(in, t, lc, s0, s1);
   } else if (kind == KIND_SPHERE) {
     if (COUNT) lc.sphere_tests++;
     float th;
@@ -341,7 +425,7 @@ MRT_HD void trav_prim_index(const TravIn& in, Trav& t, LocalCounters& lc) {
     t.i = s1.y;
   } else if (RNG && kind == KIND_VOLUME) {
     float th;
-    if (volume_hit(S, in, t, s0, s1.x, th)) {
+    if (VBLAS && s1.z ? volume_hit_blas<COUNT, ALPHA, LDS>(S, in, t, lc, s0, s1, th) : volume_hit(S, in, t, s0, s1.x, th)) {
       t.best = th;
       t.prim = make_ref(MRT_REF_VOLUME, s1.x);
       t.hit_ret = t.ret;

@@ -305,6 +305,24 @@ int mrt_builder_add_instance(mrt_builder* b, int model, const float* translation
   });
 }
 
+int mrt_builder_add_volume_instance(mrt_builder* b, int model, const float* translation, const float* rotation,
+                                    const float* scale, float density, const float* albedo) {
+  return guard(b, [&] {
+    if (model < 0 || (size_t)model >= b->models.size()) throw Error(MRT_ERR_INVALID, "model index out of range");
+    if (!translation || !rotation || !scale || !albedo) throw Error(MRT_ERR_INVALID, "null argument");
+    const InstanceDesc d = b->models[model].instance(v3p(translation), v3p(rotation), v3p(scale));
+    return (int)b->world->add_volume(d, density, v3p(albedo));
+  });
+}
+
+int mrt_builder_add_volume_model(mrt_builder* b, int model, float density, const float* albedo) {
+  return guard(b, [&] {
+    if (model < 0 || (size_t)model >= b->models.size()) throw Error(MRT_ERR_INVALID, "model index out of range");
+    if (!albedo) throw Error(MRT_ERR_INVALID, "null argument");
+    return (int)b->world->add_volume(b->models[model], density, v3p(albedo));
+  });
+}
+
 int mrt_builder_camera(mrt_builder* b, float vfov, const float* from, const float* at, const float* up, float aspect,
                        float aperture, float focus) {
   return guard(b, [&] {
@@ -377,6 +395,17 @@ int mrt_builder_desc_ext(mrt_builder* b, mrt_scene_ext* ext) {
     if (!ext) throw Error(MRT_ERR_INVALID, "null output");
     b->world->desc();  // interns what the objects reference
     *ext = b->world->desc_ext();
+    return 0;
+  });
+  return rc < 0 ? -rc : rc;
+}
+
+int mrt_builder_volume_targets(mrt_builder* b, const mrt_volume_target** targets, uint32_t* n) {
+  int rc = guard(b, [&] {
+    if (!targets || !n) throw Error(MRT_ERR_INVALID, "null output");
+    const std::vector<mrt_volume_target>& t = b->world->volume_targets();
+    *targets = t.empty() ? nullptr : t.data();
+    *n = (uint32_t)t.size();
     return 0;
   });
   return rc < 0 ? -rc : rc;

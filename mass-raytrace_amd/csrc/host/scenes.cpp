@@ -1,6 +1,8 @@
 // scenes.cpp — built-in scenes written against the host trait-surface mirror.
 //   sphere_grid  = SphereGrid::generate   /root/reference/src/scenes/sphere_grid.rs:23-94
 //   cornell      = CornellBox::generate   scenes/cornell.rs:20-99
+//   cornell_smoke = the same with two fog boxes: Volume(cube.instance(..), 0.35, albedo)
+//                  in place of the glass sphere (albedo 1) and the tall box (albedo 0)
 //   cube_field   = BASELINE config 3: 10,000 cube.ply instances (lucy.rs:52-77 pattern)
 //   mesh_ply     = BASELINE config 4: synthetic 1M-triangle binary PLY + 2 area lights
 //   mesh_obj     = config 4 through obj_loader (v/vt/vn, obj_fns + Lambertian(SolidColor))
@@ -72,7 +74,9 @@ SceneResult sphere_grid(float aspect, const std::string& assets, uint64_t seed) 
   return r;
 }
 
-SceneResult cornell(float aspect, const std::string& assets, uint64_t seed) {
+// smoke: the two fog boxes of the Cornell "smoke box" in place of the glass
+// sphere and the tall white box, in the same places of the add order
+SceneResult cornell(float aspect, const std::string& assets, uint64_t seed, bool smoke) {
   SceneResult r;
   r.world = std::make_unique<World>(SolidBackground(V3{0, 0, 0}), seed);
   World& world = *r.world;
@@ -87,9 +91,15 @@ SceneResult cornell(float aspect, const std::string& assets, uint64_t seed) {
   world.add(cube.instance(V3{0, 15, 0}, V3{0, 0, 0}, fill3(5)).with_material(white));
   world.add(cube.instance(V3{0, 5, -10}, V3{0, 0, 0}, fill3(5)).with_material(white));
   world.add(cube.instance(V3{0, -5, -0.0f}, V3{0, 0, 0}, fill3(5)).with_material(white));
-  world.add(Sphere(glass, V3{1.75f, 2.0f, 2.25f}, 2.0f));
+  if (smoke)
+    world.add_volume(cube.instance(V3{1.75f, 1.5f, 2.25f}, V3{0, 0.3f, 0}, fill3(1.5f)), 0.35f, fill3(1.0f));
+  else
+    world.add(Sphere(glass, V3{1.75f, 2.0f, 2.25f}, 2.0f));
   world.add(cube.instance(V3{0, 10.0f - 0.00011f, 0}, V3{0, 0, 0}, V3{1.0f, 0.0001f, 1.0f}).with_material(light));
-  world.add(cube.instance(V3{-2, 3, -1}, V3{0, -0.05f, 0}, V3{1.75f, 3.1f, 1.75f}).with_material(white));
+  if (smoke)
+    world.add_volume(cube.instance(V3{-2, 3, -1}, V3{0, -0.05f, 0}, V3{1.75f, 3.1f, 1.75f}), 0.35f, fill3(0.0f));
+  else
+    world.add(cube.instance(V3{-2, 3, -1}, V3{0, -0.05f, 0}, V3{1.75f, 3.1f, 1.75f}).with_material(white));
   V3 look_from{0, 5, 20}, look_at{0, 5, 0};
   r.camera = Camera::make(37.0f, look_from, look_at, V3{0, 1, 0}, aspect, 0.0f, length(look_from - look_at));
   return r;
@@ -313,7 +323,9 @@ SceneResult generate_builtin(const std::string& name, float aspect, const std::s
   if (name == "sphere_grid")
     r = sphere_grid(aspect, assets, seed);
   else if (name == "cornell")
-    r = cornell(aspect, assets, seed);
+    r = cornell(aspect, assets, seed, false);
+  else if (name == "cornell_smoke")
+    r = cornell(aspect, assets, seed, true);
   else if (name == "cube_field")
     r = cube_field(aspect, assets, seed);
   else if (name == "mesh_ply")

@@ -285,6 +285,34 @@ uint32_t World::add(const VolumeDesc& v) {
   return idx;
 }
 
+uint32_t World::add_volume_over(uint32_t target, const BoundingBox& box, float density, V3 albedo) {
+  uint32_t idx = (uint32_t)volumes_.size();
+  mrt_volume d{};  // center and radius are ignored for a listed volume
+  d.density = density;
+  d.material = intern_material(Isotrophic(albedo));
+  volumes_.push_back(d);
+  volume_targets_.push_back(mrt_volume_target{idx, target});
+  objects_.push_back(Item{MRT_REF(MRT_REF_VOLUME, idx), box});
+  return idx;
+}
+
+uint32_t World::add_volume(const InstanceDesc& target, float density, V3 albedo) {
+  uint32_t idx = (uint32_t)instances_.size();
+  mrt_instance d{};
+  put_m4(d.fwd, target.transform);
+  put_m4(d.inv, target.inv_transform);
+  d.blas_root = target.blas_root;
+  d.material = MRT_NO_MATERIAL;  // a target's material is never seen
+  instances_.push_back(d);
+  return add_volume_over(MRT_REF(MRT_REF_INSTANCE, idx), target.box, density, albedo);
+}
+
+uint32_t World::add_volume(const Model& target, float density, V3 albedo) {
+  uint32_t idx = (uint32_t)models_.size();
+  models_.push_back(mrt_model{target.blas_root, MRT_NO_MATERIAL});
+  return add_volume_over(MRT_REF(MRT_REF_MODEL, idx), target.box, density, albedo);
+}
+
 static mrt_triangle to_abi(const Triangle& t, uint32_t material) {
   mrt_triangle d{};
   put3(d.a, t.vertex_a);

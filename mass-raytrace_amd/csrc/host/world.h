@@ -332,6 +332,12 @@ class World {
   void add(const InstanceDesc& inst);
   void add(Model& m);  // World::add(model)
   uint32_t add(const VolumeDesc& v);
+  // World::add(Volume::new(target, density, albedo)) with an instance or a
+  // model as the boundary (Volume<I: Intersect>, geom.rs:595-660): the Volume
+  // owns its target, which joins instances[] / models[] but not the object
+  // list; the volume's box is the target's (geom.rs:657-659)
+  uint32_t add_volume(const InstanceDesc& target, float density, V3 albedo);
+  uint32_t add_volume(const Model& target, float density, V3 albedo);
   // Model::new / Model::with_material: builds the BLAS now (consumes RNG)
   Model model(std::vector<Triangle> triangles);
   Model model_with_material(Material m, std::vector<Triangle> triangles);
@@ -343,6 +349,8 @@ class World {
   const mrt_scene_desc& desc();
   // the tables beside it (mrt_upload_scene_ext); call after desc()
   const mrt_scene_ext& desc_ext();
+  // the volumes whose boundary is an instance or a model (mrt_upload_scene_targets)
+  const std::vector<mrt_volume_target>& volume_targets() const { return volume_targets_; }
 
   size_t n_objects() const { return objects_.size(); }
   size_t n_nodes() const { return nodes_.size(); }
@@ -361,6 +369,8 @@ class World {
   std::vector<mrt_instance> instances_;
   std::vector<mrt_model> models_;
   std::vector<mrt_volume> volumes_;
+  std::vector<mrt_volume_target> volume_targets_;
+  uint32_t add_volume_over(uint32_t target, const BoundingBox& box, float density, V3 albedo);
   std::vector<mrt_material> materials_;
   std::vector<mrt_eve_material> eve_materials_;
   mrt_scene_ext ext_{};

@@ -52,7 +52,14 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "desc_ext: %s\n", mrt_builder_last_error());
     return 1;
   }
-  if (mrt_upload_scene_ext(ctx, &desc, &ext) != MRT_OK) return fail("mrt_upload_scene_ext", ctx);
+  const mrt_volume_target* targets = nullptr;  // the fog boxes' boundaries, none for the other scenes
+  uint32_t n_targets = 0;
+  if (mrt_builder_volume_targets(b, &targets, &n_targets) != MRT_OK) {
+    std::fprintf(stderr, "volume_targets: %s\n", mrt_builder_last_error());
+    return 1;
+  }
+  if (mrt_upload_scene_targets(ctx, &desc, &ext, targets, n_targets) != MRT_OK)
+    return fail("mrt_upload_scene_targets", ctx);
   if (mrt_set_camera(ctx, &cam) != MRT_OK) return fail("mrt_set_camera", ctx);
   mrt_builder_free(b);
 

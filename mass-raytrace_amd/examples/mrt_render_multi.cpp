@@ -60,7 +60,10 @@ int main(int argc, char** argv) {
   if (mrt_create_multi((int)devs.size(), devs.data(), &ctx) != MRT_OK) die("mrt_create_multi", nullptr);
   mrt_scene_ext ext;  // the Eve table, empty for the other scenes
   if (mrt_builder_desc_ext(b, &ext) != MRT_OK) die("mrt_builder_desc_ext", nullptr);
-  if (mrt_upload_scene_ext(ctx, &desc, &ext) != MRT_OK) die("mrt_upload_scene_ext", ctx);
+  const mrt_volume_target* targets = nullptr;  // the fog boxes' boundaries, none for the other scenes
+  uint32_t n_targets = 0;
+  if (mrt_builder_volume_targets(b, &targets, &n_targets) != MRT_OK) die("mrt_builder_volume_targets", nullptr);
+  if (mrt_upload_scene_targets(ctx, &desc, &ext, targets, n_targets) != MRT_OK) die("mrt_upload_scene_targets", ctx);
   if (mrt_set_camera(ctx, &cam) != MRT_OK) die("mrt_set_camera", ctx);
   mrt_builder_free(b);
   mrt_image* img = nullptr;

@@ -122,6 +122,10 @@ class MrtSceneExt(C.Structure):
     _fields_ = [("eve_materials", C.POINTER(MrtEveMaterial)), ("n_eve_materials", C.c_uint32)]
 
 
+class MrtVolumeTarget(C.Structure):
+    _fields_ = [("volume", C.c_uint32), ("target", C.c_uint32)]
+
+
 SHADE_FRONT_FACE, SHADE_HAS_UV, SHADE_SCATTERED = 1, 2, 4
 
 
@@ -256,6 +260,8 @@ EXPORTED_SYMBOLS = [
     "mrt_denoise_default_params", "mrt_denoise_device", "mrt_denoise", "mrt_image_set_denoise",
     "mrt_upload_scene_ext", "mrt_shade_rays", "mrt_builder_eve_material", "mrt_builder_desc_ext",
     "mrt_load_obj_groups",
+    "mrt_upload_scene_targets", "mrt_builder_add_volume_instance", "mrt_builder_add_volume_model",
+    "mrt_builder_volume_targets",
 ]
 
 _lib = None
@@ -358,6 +364,11 @@ def lib() -> C.CDLL:
         "mrt_builder_eve_material": (I, [P, U32, U32, U32, fp, fp]),
         "mrt_builder_desc_ext": (I, [P, C.POINTER(MrtSceneExt)]),
         "mrt_load_obj_groups": (I64, [C.c_char_p, C.POINTER(C.c_char_p), U32, fp, U64]),
+        "mrt_upload_scene_targets": (I, [P, C.POINTER(MrtSceneDesc), C.POINTER(MrtSceneExt),
+                                         C.POINTER(MrtVolumeTarget), U32]),
+        "mrt_builder_add_volume_instance": (I, [P, I, fp, fp, fp, F, fp]),
+        "mrt_builder_add_volume_model": (I, [P, I, F, fp]),
+        "mrt_builder_volume_targets": (I, [P, C.POINTER(C.POINTER(MrtVolumeTarget)), C.POINTER(U32)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -485,6 +496,23 @@ class Builder:
         """World::add(Volume::new(Sphere(center, radius), density, albedo)) (geom.rs:595-653)."""
         return _check_builder(lib().mrt_builder_add_volume(self.h, _fptr(_f3(center)), float(radius), float(density),
                                                            _fptr(_f3(albedo))))
+
+    def add_volume_instance(self, model, translation, rotation, scale, density, albedo) -> int:
+        """World::add(Volume::new(model.instance(t, r, s), density, albedo)): a fog box; returns the volume index."""
+        t, r, s = _f3(translation), _f3(rotation), _f3(scale)
+        return _check_builder(lib().mrt_builder_add_volume_instance(self.h, model, _fptr(t), _fptr(r), _fptr(s),
+                                                                    float(density), _fptr(_f3(albedo))))
+
+    def add_volume_model(self, model, density, albedo) -> int:
+        """World::add(Volume::new(model, density, albedo)); returns the volume index."""
+        return _check_builder(lib().mrt_builder_add_volume_model(self.h, model, float(density), _fptr(_f3(albedo))))
+
+    def volume_targets(self):
+        """(pointer, count) of the mrt_volume_target table (mrt_upload_scene_targets); valid as desc() is."""
+        p, n = C.POINTER(MrtVolumeTarget)(), C.c_uint32()
+        if lib().mrt_builder_volume_targets(self.h, C.byref(p), C.byref(n)) != 0:
+            raise MassrtError(lib().mrt_builder_last_error().decode())
+        return p, int(n.value)
 
     def add_triangle(self, material, abc):
         a = np.ascontiguousarray(np.asarray(abc, dtype=np.float32).reshape(9))
@@ -657,11 +685,17 @@ class Context:
     def upload(self, builder: Builder):
         d, cam = builder.desc()
         ext = builder.desc_ext()
-        self._check(lib().mrt_upload_scene_ext(self.h, C.byref(d), C.byref(ext)))
+        targets, n = builder.volume_targets()
+        self._check(lib().mrt_upload_scene_targets(self.h, C.byref(d), C.byref(ext), targets, n))
         self._check(lib().mrt_set_camera(self.h, C.byref(cam)))
 
-    def upload_desc(self, desc: MrtSceneDesc, ext: MrtSceneExt | None = None):
-        if ext is None:
+    def upload_desc(self, desc: MrtSceneDesc, ext: MrtSceneExt | None = None, targets=None):
+        """targets: [(volume, MRT_REF(INSTANCE | MODEL, index)), ...] (mrt_upload_scene_targets)."""
+        if targets is not None:
+            t = (MrtVolumeTarget * max(len(targets), 1))(*[MrtVolumeTarget(int(v), int(r)) for v, r in targets])
+            self._check(lib().mrt_upload_scene_targets(self.h, C.byref(desc), None if ext is None else C.byref(ext), t,
+                                                       len(targets)))
+        elif ext is None:
             self._check(lib().mrt_upload_scene(self.h, C.byref(desc)))
         else:
             self._check(lib().mrt_upload_scene_ext(self.h, C.byref(desc), C.byref(ext)))
