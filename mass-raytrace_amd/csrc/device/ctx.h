@@ -9,6 +9,7 @@
 #include <map>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -174,6 +175,17 @@ int on_each(mrt_ctx* c, F&& f) {
   if ((c) && (c)->multi) return on_dev0((c), [&](mrt_ctx* c) { return call; })
 #define MRT_EACH(c, call) \
   if ((c) && (c)->multi) return on_each((c), [&](mrt_ctx* c) { return call; })
+
+// A runtime value as a template argument, for choosing among a kernel's
+// variants: f(std::integral_constant<V>) for the first of V, Vs... that equals
+// v, for the last if none does.
+template <auto V, auto... Vs, typename T, typename F>
+auto with_value(T v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0)
+    return f(std::integral_constant<decltype(V), V>{});
+  else
+    return v == V ? f(std::integral_constant<decltype(V), V>{}) : with_value<Vs...>(v, f);
+}
 
 // ---- trace.hip ----
 // k_trace over pool buffer `in` of queue `q`, specialised on the scene, on stream `st`

@@ -43,7 +43,7 @@ __device__ __forceinline__ void gen_work(const DevCamera& cam, const RenderParam
   camera_ray(cam, x, y, rp.W, rp.H, rng, o, d);
   ro = make_float4(o.x, o.y, o.z, __uint_as_float(g));
   rd = make_float4(d.x, d.y, d.z, __uint_as_float(0u));
-  rs = make_uint4((uint32_t)rng.s0, (uint32_t)(rng.s0 >> 32), (uint32_t)rng.s1, (uint32_t)(rng.s1 >> 32));
+  rs = rng_pack(rng);
 }
 
 // Initial pool: work items [base, base + n0) into slots [0, n0).
@@ -180,8 +180,7 @@ __global__ __launch_bounds__(kShadeBlock, WPE) void k_shade(DevScene S, RenderPa
       Hit h{__uint_as_float(hv.x), hv.y, hv.z};
       V3 o{ro.x, ro.y, ro.z}, d{rd.x, rd.y, rd.z}, T{thr.x, thr.y, thr.z}, L{rad.x, rad.y, rad.z};
       uint32_t g = __float_as_uint(ro.w), k = __float_as_uint(rd.w);
-      PathRng rng{(unsigned long long)rs.x | ((unsigned long long)rs.y << 32),
-                  (unsigned long long)rs.z | ((unsigned long long)rs.w << 32)};
+      PathRng rng = rng_unpack(rs);
       const bool cont = shade_step<EXT>(S, rp.max_depth, h, o, d, T, L, k, rng, lc, nbounce, mat, mkind);
       if (cont) {
         alive = true;
@@ -189,7 +188,7 @@ __global__ __launch_bounds__(kShadeBlock, WPE) void k_shade(DevScene S, RenderPa
         rd = make_float4(d.x, d.y, d.z, __uint_as_float(k));
         thr = make_float4(T.x, T.y, T.z, __uint_as_float(nonzero_bits(L.x, L.y, L.z) ? kHoldsL : 0u));
         rad = make_float4(L.x, L.y, L.z, 0.0f);
-        rs = make_uint4((uint32_t)rng.s0, (uint32_t)(rng.s0 >> 32), (uint32_t)rng.s1, (uint32_t)(rng.s1 >> 32));
+        rs = rng_pack(rng);
       } else {
 #ifndef MRT_PROBE_NO_RESULTS  // probe build (tools/shade_probe.sh): k_shade's HBM writes without the scattered results stores
         results[MRT_IDX(S, g, rp.G, 21)] = make_float4(L.x, L.y, L.z, __uint_as_float(k));
@@ -294,8 +293,7 @@ __global__ __launch_bounds__(kBlock) void k_render(DevScene S, DevCamera cam, Re
             T = V3{1.0f, 1.0f, 1.0f};
             L = V3{0.0f, 0.0f, 0.0f};
           }
-          rng = PathRng{(unsigned long long)rs.x | ((unsigned long long)rs.y << 32),
-                        (unsigned long long)rs.z | ((unsigned long long)rs.w << 32)};
+          rng = rng_unpack(rs);
           slot_ro[slot] = ro;
           slot_rd[slot] = rd;
           trav_init(tin, t, slot, INFINITY);
@@ -389,18 +387,20 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(const float4* results, ui
 using ShadeFn = void (*)(DevScene, RenderParams, PathBufs, PathBufs, const uint4*, Ctrl*, uint32_t, float4*,
                          DevCounters*);
 ShadeFn shade_kernel(bool count, bool ext, int wpe) {
-  return wpe == 7 ? (count ? (ext ? k_shade<true, true, 7> : k_shade<true, false, 7>)
-                           : (ext ? k_shade<false, true, 7> : k_shade<false, false, 7>))
-                  : (count ? (ext ? k_shade<true, true, 8> : k_shade<true, false, 8>)
-                           : (ext ? k_shade<false, true, 8> : k_shade<false, false, 8>));
+  return with_value<true, false>(count, [&](auto COUNT) {
+    return with_value<true, false>(ext, [&](auto EXT) {
+      return with_value<7, 8>(wpe, [&](auto WPE) -> ShadeFn { return k_shade<COUNT, EXT, WPE>; });
+    });
+  });
 }
 using RenderFn = void (*)(DevScene, DevCamera, RenderParams, float4*, float4*, Ctrl*, float4*, DevCounters*,
                           TraceTune, PathBufs, uint32_t);
 RenderFn render_kernel(bool count, bool alpha, bool adopt) {
-  return count ? (alpha ? (adopt ? k_render<true, true, true> : k_render<true, true, false>)
-                        : (adopt ? k_render<true, false, true> : k_render<true, false, false>))
-               : (alpha ? (adopt ? k_render<false, true, true> : k_render<false, true, false>)
-                        : (adopt ? k_render<false, false, true> : k_render<false, false, false>));
+  return with_value<true, false>(count, [&](auto COUNT) {
+    return with_value<true, false>(alpha, [&](auto ALPHA) {
+      return with_value<true, false>(adopt, [&](auto ADOPT) -> RenderFn { return k_render<COUNT, ALPHA, ADOPT>; });
+    });
+  });
 }
 
 // k_shade's grid for a pool known to hold at most `bound` live paths: one

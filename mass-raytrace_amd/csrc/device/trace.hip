@@ -26,8 +26,7 @@ constexpr uint32_t kStashQuads = 4;  // float4s per lane of the world-ray stash 
 
 // RNG: the scene's traversal draws random numbers (Volume, Mix alpha tests):
 // each ray carries its path stream through the traversal and stores it back.
-// (R > 1 would interleave R rays per lane — software ILP; measured slower at
-// its 84 VGPRs, so only R = 1 is instantiated.)
+// (One ray per lane: two, interleaved for ILP, were measured slower at 84 VGPRs.)
 // NF: the verified near-first walk (walk_nf.h trav_*_nf): the SAH trees walked
 // near child first with a per-lane stack in LDS (kNfStack x BLK words of
 // dynamic shared memory), the winner checked against the reference tree,
@@ -38,7 +37,6 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(NF ? (COUNT
   static_assert(!NF || (!LDS && !RNG), "the near-first walk has no treelet and no traversal draws");
   static_assert(!WILD || NF, "only the near-first walk has a wild tree");
   static_assert(!VBLAS || RNG, "a volume draws");
-  constexpr int R = 1;
   const uint32_t n = ctrl->active[cur];
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     ctrl->active[cur ^ 1] = 0;
@@ -66,22 +64,17 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(NF ? (COUNT
   // contiguous eighth keeps an XCD's rays — and the scene parts they touch —
   // together in that XCD's L2. A group whose eighth is taken helps the next.
   uint32_t grp = blockIdx.x % kGroups, visited = 0;  // wave-uniform
-  Trav t[R];
-#pragma unroll
-  for (int q = 0; q < R; ++q) {
-    t[q] = Trav{};  // fully initialised: idle lanes must not carry undefined state
-    t[q].done = true;
-    t[q].ray = kIdle;
-  }
+  Trav t{};  // fully initialised: idle lanes must not carry undefined state
+  t.done = true;
+  t.ray = kIdle;
+  // The loop's phases, in order: refill, box run, mixed step / primitive run,
+  // near-first batches, retire. They stay inline: as lambdas called from the
+  // loop, the same statements made k_trace 1.7% slower on cube_field.
   for (;;) {
-    unsigned long long idle[R];
-    uint32_t n_idle = 0;
-#pragma unroll
-    for (int q = 0; q < R; ++q) {
-      idle[q] = __ballot(t[q].ray == kIdle);
-      n_idle += (uint32_t)__popcll(idle[q]);
-    }
-    if (n_idle >= tune.refill * R || n_idle == 64u * R) {
+    // refill: once enough lanes are idle, the wave's next chunk starts on them
+    const unsigned long long idle = __ballot(t.ray == kIdle);
+    const uint32_t n_idle = (uint32_t)__popcll(idle);
+    if (n_idle >= tune.refill || n_idle == 64u) {
       while (pool == pool_end && !drained) {  // grab the next chunk (wave-uniform)
         const uint32_t lo = (uint32_t)((uint64_t)n * grp / kGroups), hi = (uint32_t)((uint64_t)n * (grp + 1) / kGroups);
         uint32_t b = 0;
@@ -97,139 +90,112 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(NF ? (COUNT
         }
       }
       const uint32_t avail = pool_end - pool;
-      uint32_t off = 0;
-      unsigned long long live = 0;
-#pragma unroll
-      for (int q = 0; q < R; ++q) {
-        if (t[q].ray == kIdle) {
-          const uint32_t r = off + lane_rank(idle[q]);
-          if (r < avail) {
-            if constexpr (NF)
-              trav_init_nf<WILD>(tin, stk, t[q], MRT_IDX(S, pool + r, n, 20), tmax, S.nf_world);
-            else
-              trav_init<RNG, LDS>(tin, t[q], MRT_IDX(S, pool + r, n, 20), tmax);
-          }
+      if (t.ray == kIdle) {
+        const uint32_t r = lane_rank(idle);
+        if (r < avail) {
+          if constexpr (NF)
+            trav_init_nf<WILD>(tin, stk, t, MRT_IDX(S, pool + r, n, 20), tmax, S.nf_world);
+          else
+            trav_init<RNG, LDS>(tin, t, MRT_IDX(S, pool + r, n, 20), tmax);
         }
-        off += (uint32_t)__popcll(idle[q]);
-        live |= __ballot(t[q].ray != kIdle);
       }
       pool += n_idle < avail ? n_idle : avail;
-      if (live == 0) break;  // chunk source exhausted
+      if (__ballot(t.ray != kIdle) == 0) break;  // chunk source exhausted
     }
-#pragma unroll
-    for (int q = 0; q < R; ++q) {
-      // box run: keep stepping boxes with little per-step overhead while at
-      // least tune.box_min lanes are at one (lanes reaching a primitive wait)
-      // Two steps per loop iteration: with one, the compiler carried the
-      // record just loaded into the loop-header registers with 8 v_mov per
-      // step; unrolled, the two steps alternate register sets and the copies
-      // are gone (sphere_grid 671 -> 703, cube_field 254 -> 266, mesh_ply
-      // 740 -> 749 Msamples/s, same box).
-      auto box_step = [&]() {  // false: too few lanes at a box
-        // a done lane holds an END record (or an idle lane's zeros), never a
-        // box, so the record's flag alone decides (no done mask in the ballot)
-        const bool run_box = trav_at_box(t[q]);
-        const unsigned long long bm = __builtin_amdgcn_ballot_w64(run_box);
-        if ((uint32_t)__popcll(bm) < tune.box_min) return false;
-        if (run_box) {
-          if (NF && t[q].sp != kExactMode)
-            trav_box_index_nf<COUNT, WILD>(tin, stk, t[q], lc);
-          else
-            trav_box_index<COUNT>(tin, t[q], lc);
-        }
-        if (run_box && (!NF || !nf_parked<WILD>(t[q]))) trav_fetch<LDS>(tin, t[q]);
-        if (COUNT) {
-          lc.wave_slots += lane_id() == 0 ? 64u : 0u;
-          lc.lane_steps += run_box ? 1u : 0u;
-        }
-        return true;
+    // box run: keep stepping boxes with little per-step overhead while at
+    // least tune.box_min lanes are at one (lanes reaching a primitive wait)
+    // Two steps per loop iteration: with one, the compiler carried the
+    // record just loaded into the loop-header registers with 8 v_mov per
+    // step; unrolled, the two steps alternate register sets and the copies
+    // are gone (sphere_grid 671 -> 703, cube_field 254 -> 266, mesh_ply
+    // 740 -> 749 Msamples/s, same box).
+    auto box_step = [&]() {  // false: too few lanes at a box
+      // a done lane holds an END record (or an idle lane's zeros), never a
+      // box, so the record's flag alone decides (no done mask in the ballot)
+      const bool run_box = trav_at_box(t);
+      const unsigned long long bm = __builtin_amdgcn_ballot_w64(run_box);
+      if ((uint32_t)__popcll(bm) < tune.box_min) return false;
+      if (run_box) trav_box_index_either<COUNT, NF, WILD>(tin, stk, t, lc);
+      // (a lane at a box is not done: of trav_may_fetch only the waiting is asked)
+      if (run_box && (!NF || !nf_parked<WILD>(t))) trav_fetch<LDS>(tin, t);
+      if (COUNT) {
+        lc.wave_slots += lane_id() == 0 ? 64u : 0u;
+        lc.lane_steps += run_box ? 1u : 0u;
+      }
+      return true;
+    };
+    while (box_step() && box_step()) {
+    }
+    // idle lanes hold a done Trav; a near-first lane whose walk is over
+    // waits for the check below.
+    // One step per busy lane (a box, or a primitive once enough lanes wait
+    // at one or no lane is at a box), then ONE record fetch for every lane
+    // that moved: the address unit costs per wave instruction, so the box
+    // and primitive lanes share the load pair instead of issuing one each.
+    // Primitive run (the box run's mirror): while at least tune.prim_run
+    // lanes are at a primitive, they step alone (a leaf's primitives one
+    // after another) instead of paying the box branch beside each step —
+    // the same code with the box lanes masked off, so nothing is inlined
+    // twice. Every pass steps a lane: while the run is on, tune.prim_run >=
+    // tune.prim_batch (options.h derive_tuning), so its lanes have prim_go.
+    for (;;) {
+      const bool busy = trav_may_fetch<NF, WILD>(t);
+      const bool at_box = busy && trav_at_box(t);
+      const unsigned long long box_mask = __ballot(at_box);
+      const unsigned long long prim_mask = __ballot(busy && !at_box);
+      // (the near-first walk only: the reference walk's k_trace, compiled
+      // with this loop, lost 14% — 971 -> 832 on sphere_grid at any
+      // threshold, profiles/r6_primrun/ — so there it folds to one step)
+      const bool prim_run = NF && (uint32_t)__popcll(prim_mask) >= tune.prim_run;  // wave-uniform
+      const bool box_go = at_box && !prim_run;
+      const bool prim_go = (__popcll(prim_mask) >= tune.prim_batch || box_mask == 0) && busy && !at_box;
+      if (box_go) trav_box_index_either<COUNT, NF, WILD>(tin, stk, t, lc);
+      if (prim_go) trav_prim_index_either<COUNT, ALPHA, RNG, LDS, VBLAS, NF, WILD>(tin, stk, t, lc);
+      if ((box_go || prim_go) && trav_may_fetch<NF, WILD>(t)) trav_fetch<LDS>(tin, t);
+      if (COUNT) {
+        lc.wave_slots += lane_id() == 0 ? 64u : 0u;
+        lc.lane_steps += (box_go || prim_go) ? 1u : 0u;
+      }
+      if (!prim_run) break;
+    }
+    // near-first walks that are over: check their hits (done, or the
+    // reference's walk from the start) — batched: the check is a few
+    // hundred wave instructions, so finished lanes wait (holding an END
+    // record) until tune.nf_batch of them can share one pass, or until no
+    // lane is walking any more
+    if (NF) {
+      // lanes that have walked everything but the wild instances' tree
+      // (walk_nf.h kNfWait) enter it as a batch, for the same reason: a
+      // wild leaf's box test, the entry and the exit are the walk's longest
+      // steps, and a wave pays for each once per pass, however few lanes
+      // take it. Entered one lane at a time, as each ray's stack ran out,
+      // they cost sphere_grid 15% of k_trace's time for 12% fewer box
+      // tests; batched at nf_batch, -2.5% (at half of it +1.8%, at a
+      // quarter +7%: DESIGN.md §5).
+      // this lane's batch (the lanes holding `mine`) goes once nf_batch of them
+      // wait, or when none of the lanes `others()` is left to wait for
+      auto batch_go = [&](bool mine, auto others) {
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(mine);
+        return m != 0 && ((uint32_t)__popcll(m) >= tune.nf_batch || __builtin_amdgcn_ballot_w64(others()) == 0) && mine;
       };
-      while (box_step() && box_step()) {
+      if (WILD && batch_go(t.sp == kNfWait, [&]() { return trav_may_fetch<NF, WILD>(t); })) {
+        nf_resume_wild(tin, t);
+        trav_fetch<LDS>(tin, t);
       }
-      // idle lanes hold a done Trav; a near-first lane whose walk is over
-      // waits for the check below.
-      // One step per busy lane (a box, or a primitive once enough lanes wait
-      // at one or no lane is at a box), then ONE record fetch for every lane
-      // that moved: the address unit costs per wave instruction, so the box
-      // and primitive lanes share the load pair instead of issuing one each.
-      // Primitive run (the box run's mirror): while at least tune.prim_run
-      // lanes are at a primitive, they step alone (a leaf's primitives one
-      // after another) instead of paying the box branch beside each step —
-      // the same code with the box lanes masked off, so nothing is inlined
-      // twice. Every pass steps a lane: while the run is on, tune.prim_run >=
-      // tune.prim_batch (options.h derive_tuning), so its lanes have prim_go.
-      for (;;) {
-        const bool busy = !t[q].done && (!NF || !nf_parked<WILD>(t[q]));
-        const bool at_box = busy && trav_at_box(t[q]);
-        const unsigned long long box_mask = __ballot(at_box);
-        const unsigned long long prim_mask = __ballot(busy && !at_box);
-        // (the near-first walk only: the reference walk's k_trace, compiled
-        // with this loop, lost 14% — 971 -> 832 on sphere_grid at any
-        // threshold, profiles/r6_primrun/ — so there it folds to one step)
-        const bool prim_run = NF && (uint32_t)__popcll(prim_mask) >= tune.prim_run;  // wave-uniform
-        const bool box_go = at_box && !prim_run;
-        const bool prim_go = (__popcll(prim_mask) >= tune.prim_batch || box_mask == 0) && busy && !at_box;
-        if (box_go) {
-          if (NF && t[q].sp != kExactMode)
-            trav_box_index_nf<COUNT, WILD>(tin, stk, t[q], lc);
-          else
-            trav_box_index<COUNT>(tin, t[q], lc);
-        }
-        if (prim_go) {
-          if (NF && t[q].sp != kExactMode)
-            trav_prim_index_nf<COUNT, ALPHA, WILD>(tin, stk, t[q], lc);
-          else
-            trav_prim_index<COUNT, ALPHA, RNG, LDS, VBLAS>(tin, t[q], lc);
-        }
-        if ((box_go || prim_go) && !t[q].done && (!NF || !nf_parked<WILD>(t[q]))) trav_fetch<LDS>(tin, t[q]);
-        if (COUNT) {
-          lc.wave_slots += lane_id() == 0 ? 64u : 0u;
-          lc.lane_steps += (box_go || prim_go) ? 1u : 0u;
-        }
-        if (!prim_run) break;
-      }
-      // near-first walks that are over: check their hits (done, or the
-      // reference's walk from the start) — batched: the check is a few
-      // hundred wave instructions, so finished lanes wait (holding an END
-      // record) until tune.nf_batch of them can share one pass, or until no
-      // lane is walking any more
-      if (NF) {
-        // lanes that have walked everything but the wild instances' tree
-        // (walk_nf.h kNfWait) enter it as a batch, for the same reason: a
-        // wild leaf's box test, the entry and the exit are the walk's longest
-        // steps, and a wave pays for each once per pass, however few lanes
-        // take it. Entered one lane at a time, as each ray's stack ran out,
-        // they cost sphere_grid 15% of k_trace's time for 12% fewer box
-        // tests; batched at nf_batch, -2.5% (at half of it +1.8%, at a
-        // quarter +7%: DESIGN.md §5).
-        if (WILD) {
-          const bool wait = t[q].sp == kNfWait;
-          const unsigned long long wm = __builtin_amdgcn_ballot_w64(wait);
-          if (wm != 0 && ((uint32_t)__popcll(wm) >= tune.nf_batch ||
-                          __builtin_amdgcn_ballot_w64(!t[q].done && !nf_parked<WILD>(t[q])) == 0) && wait) {
-            nf_resume_wild(tin, t[q]);
-            trav_fetch<LDS>(tin, t[q]);
-          }
-        }
-        const bool over = t[q].sp == kNfDone;
-        const unsigned long long om = __builtin_amdgcn_ballot_w64(over);
-        if (om != 0 && ((uint32_t)__popcll(om) >= tune.nf_batch ||
-                        __builtin_amdgcn_ballot_w64(!t[q].done && !over) == 0) && over) {
-          nf_finish<COUNT>(tin, t[q], lc);
-          if (!t[q].done) trav_fetch<LDS>(tin, t[q]);
-        }
+      const bool over = t.sp == kNfDone;
+      if (batch_go(over, [&]() { return !t.done && !over; })) {
+        nf_finish<COUNT>(tin, t, lc);
+        if (!t.done) trav_fetch<LDS>(tin, t);
       }
     }
-#pragma unroll
-    for (int q = 0; q < R; ++q) {
-      if (t[q].ray != kIdle && t[q].done) {
-        if (RNG) trav_store_rng(tin, t[q]);
-        const Hit h = trav_hit<LDS>(tin, t[q]);
-        hits[t[q].ray] = make_uint4(__float_as_uint(h.t), h.prim, h.container, 0u);
-        seg += 1;
-        nh += t[q].prim != kRefNone;
-        t[q].ray = kIdle;
-      }
+    // retire: finished rays' hits out, their lanes idle
+    if (t.ray != kIdle && t.done) {
+      if (RNG) trav_store_rng(tin, t);
+      const Hit h = trav_hit<LDS>(tin, t);
+      hits[t.ray] = make_uint4(__float_as_uint(h.t), h.prim, h.container, 0u);
+      seg += 1;
+      nh += t.prim != kRefNone;
+      t.ray = kIdle;
     }
   }
   if (COUNT) flush_counters(cnt, lc, seg, nh, 0, 0);
@@ -250,14 +216,9 @@ __global__ __launch_bounds__(kBlock) void k_trace_simple(DevScene S, PathBufs in
   const TravIn tin{S, reinterpret_cast<const uint4*>(S.slots), S.world_begin, in.ro, in.rd, kTmin, in.rng};
   for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
     PathRng rng{0, 0};
-    if (RNG) {
-      const uint4 q = in.rng[i];
-      rng = PathRng{(unsigned long long)q.x | ((unsigned long long)q.y << 32),
-                    (unsigned long long)q.z | ((unsigned long long)q.w << 32)};
-    }
+    if (RNG) rng = rng_unpack(in.rng[i]);
     Hit h = closest_hit<true, RNG>(tin, i, INFINITY, lc, rng);
-    if (RNG)
-      in.rng[i] = make_uint4((uint32_t)rng.s0, (uint32_t)(rng.s0 >> 32), (uint32_t)rng.s1, (uint32_t)(rng.s1 >> 32));
+    if (RNG) in.rng[i] = rng_pack(rng);
     hits[i] = make_uint4(__float_as_uint(h.t), h.prim, h.container, 0u);
     seg += 1;
     nh += h.prim != kRefNone;
@@ -273,8 +234,7 @@ __global__ __launch_bounds__(kBlock) void k_rays_in(const float* rays, uint32_t 
   const float* r = rays + 6 * (size_t)i;
   out.ro[i] = make_float4(r[0], r[1], r[2], __uint_as_float(i));
   out.rd[i] = make_float4(r[3], r[4], r[5], __uint_as_float(0u));
-  const PathRng g = path_rng(0, i, 0xFFFFFFFEu);  // traversal draws of mrt_trace_rays (massrt.h)
-  out.rng[i] = make_uint4((uint32_t)g.s0, (uint32_t)(g.s0 >> 32), (uint32_t)g.s1, (uint32_t)(g.s1 >> 32));
+  out.rng[i] = rng_pack(path_rng(0, i, 0xFFFFFFFEu));  // traversal draws of mrt_trace_rays (massrt.h)
 }
 
 template <bool EXT>
@@ -297,34 +257,26 @@ __global__ __launch_bounds__(kBlock) void k_rays_out(DevScene S, PathBufs in, co
 // none / plain surfaces / composite surfaces (EXT); traversal draws; or the
 // near-first walk (scenes with NF trees, no treelet, no traversal draws).
 using TraceFn = void (*)(DevScene, PathBufs, uint4*, Ctrl*, uint32_t, DevCounters*, float, float, TraceTune);
-// RNG: 0 no traversal draws, 1 draws, 2 draws and volumes whose target is a
-// BLAS (VBLAS: the nested searches of walk.h volume_hit_blas cost registers,
-// so scenes without such a volume keep the kernels they had)
-template <bool COUNT, uint32_t ALPHA, uint32_t RNG>
-TraceFn trace_kernel_lds(int block) {
-  return block == 1024  ? k_trace<COUNT, true, ALPHA, RNG != 0, 1024, false, false, RNG == 2>
-         : block == 512 ? k_trace<COUNT, true, ALPHA, RNG != 0, 512, false, false, RNG == 2>
-                        : k_trace<COUNT, true, ALPHA, RNG != 0, kBlock, false, false, RNG == 2>;
-}
-template <bool COUNT, uint32_t ALPHA>
-TraceFn trace_kernel_a(bool lds, uint32_t rng, int block, bool nf, bool wild) {
-  if (nf) return wild ? k_trace<COUNT, false, ALPHA, false, kBlock, true, true> : k_trace<COUNT, false, ALPHA, false, kBlock, true, false>;
-  if (lds)
-    return rng == 2   ? trace_kernel_lds<COUNT, ALPHA, 2>(block)
-           : rng == 1 ? trace_kernel_lds<COUNT, ALPHA, 1>(block)
-                      : trace_kernel_lds<COUNT, ALPHA, 0>(block);
-  return rng == 2   ? k_trace<COUNT, false, ALPHA, true, kBlock, false, false, true>
-         : rng == 1 ? k_trace<COUNT, false, ALPHA, true, kBlock>
-                    : k_trace<COUNT, false, ALPHA, false, kBlock>;
-}
-template <bool COUNT>
-TraceFn trace_kernel_c(bool lds, uint32_t alpha, uint32_t rng, int block, bool nf, bool wild) {
-  return alpha == 2   ? trace_kernel_a<COUNT, 2>(lds, rng, block, nf, wild)
-         : alpha == 1 ? trace_kernel_a<COUNT, 1>(lds, rng, block, nf, wild)
-                      : trace_kernel_a<COUNT, 0>(lds, rng, block, nf, wild);
-}
-TraceFn trace_kernel(bool count, bool lds, uint32_t alpha, uint32_t rng, int block, bool nf, bool wild) {
-  return count ? trace_kernel_c<true>(lds, alpha, rng, block, nf, wild) : trace_kernel_c<false>(lds, alpha, rng, block, nf, wild);
+// rng: the traversal draws; vblas: and some volume's target is a BLAS (the
+// nested searches of walk.h volume_hit_blas cost registers, so scenes without
+// such a volume keep the kernels they had). A workgroup larger than kBlock
+// exists only to share a treelet.
+TraceFn trace_kernel(bool count, bool lds, uint32_t alpha, bool rng, bool vblas, int block, bool nf, bool wild) {
+  return with_value<true, false>(count, [&](auto COUNT) {
+    return with_value<2u, 1u, 0u>(alpha, [&](auto ALPHA) -> TraceFn {
+      if (nf)
+        return with_value<true, false>(wild, [&](auto WILD) -> TraceFn { return k_trace<COUNT, false, ALPHA, false, kBlock, true, WILD>; });
+      return with_value<true, false>(rng, [&](auto RNG) {
+        return with_value<true, false>(vblas, [&](auto VB) {
+          return with_value<true, false>(lds, [&](auto LDS) {
+            return with_value<1024, 512, kBlock>(block, [&](auto B) -> TraceFn {
+              return k_trace<COUNT, LDS, ALPHA, RNG, LDS ? B : kBlock, false, false, RNG && VB>;  // a volume draws
+            });
+          });
+        });
+      });
+    });
+  });
 }
 
 }  // namespace
@@ -353,27 +305,34 @@ uint32_t persistent_grid(mrt_ctx* c, const void* f, size_t smem, bool shared, in
 void launch_trace(mrt_ctx* c, hipStream_t st, const Queue& q, const PathBufs& in, uint32_t cur, bool count,
                   float tmin, float tmax) {
   const Tuning& t = c->tun;
-  const bool nf = t.use_nf, lds = !nf && c->facts.treelet;
+  const bool shared = t.queues > 1;  // beside the other queues' kernels (persistent_grid)
   const uint32_t alpha = c->scene_alpha ? (c->scene_ext ? 2u : 1u) : 0u;
-  const int block = lds ? t.trace_block : kBlock;
+  const bool rng = c->facts.trav_rng, vblas = rng && c->scene_vblas;
   // a scene with a wild tree (layout.h nf_wild_root) runs the variant that walks it last, in batches; the
   // others compile none of that and keep 24 stack words (the builder leaves them the marker's word unused)
-  const bool wild = nf && c->S.nf_wild_root != 0;
-  const uint32_t rng = c->facts.trav_rng ? (c->scene_vblas ? 2u : 1u) : 0u;
-  const TraceFn f = trace_kernel(count, lds, alpha, rng, block, nf, wild);
-  // dynamic LDS: the near-first stack (kNfStack words per lane), the treelet, or the world-ray stash (4 x 16 B per lane)
-  const size_t smem = nf ? (size_t)(kNfStack - (wild ? 0u : 1u)) * block * 4 : lds ? (size_t)c->S.n_tlet * 16 : (size_t)kStashQuads * block * 16;
-  // Near-first: 24 KiB of LDS per workgroup of 256 lanes, kNfStack (25) with a
-  // wild tree, allow 6 workgroups per CU (6 x 25 = 150 of 160 KiB), i.e. 6
-  // waves per SIMD, its
-  // registers (<= 128 VGPRs: the rounding margins' state and code, round 5,
-  // would spill at 80) at least 4. Beside another queue the walk takes 3
-  // WG/CU: its vector-memory unit is the shared limit, so more of its waves
-  // buy nothing while k_shade beside it gains (profiles/r4_nf/tune.txt §6:
-  // 4 -> 3 WG/CU +0.8%, 2 WG/CU -14%)
-  uint32_t grid = persistent_grid(c, (const void*)f, smem, t.queues > 1, block, nf ? 1 : 3, nf ? 1 : 4);
-  const uint32_t nf_cap = 3u * (uint32_t)c->cus;
-  if (nf && t.queues > 1 && !t.wgs_per_cu && grid > nf_cap) grid = c->grids[std::make_pair((const void*)f, smem)] = nf_cap;
+  const bool nf = t.use_nf, wild = nf && c->S.nf_wild_root != 0;
+  const bool lds = !nf && c->facts.treelet;
+  const int block = lds ? t.trace_block : kBlock;
+  const TraceFn f = trace_kernel(count, lds, alpha, rng, vblas, block, nf, wild);
+  size_t smem;  // dynamic LDS
+  uint32_t grid;
+  if (nf) {
+    // Near-first: 24 KiB of LDS per workgroup of 256 lanes, kNfStack (25) with a
+    // wild tree, allow 6 workgroups per CU (6 x 25 = 150 of 160 KiB), i.e. 6
+    // waves per SIMD, its
+    // registers (<= 128 VGPRs: the rounding margins' state and code, round 5,
+    // would spill at 80) at least 4. Beside another queue the walk takes 3
+    // WG/CU: its vector-memory unit is the shared limit, so more of its waves
+    // buy nothing while k_shade beside it gains (profiles/r4_nf/tune.txt §6:
+    // 4 -> 3 WG/CU +0.8%, 2 WG/CU -14%)
+    smem = (size_t)(kNfStack - (wild ? 0u : 1u)) * block * 4;  // the stack's words per lane
+    grid = persistent_grid(c, (const void*)f, smem, shared, block, 1, 1);
+    const uint32_t nf_cap = 3u * (uint32_t)c->cus;
+    if (shared && !t.wgs_per_cu && grid > nf_cap) grid = c->grids[std::make_pair((const void*)f, smem)] = nf_cap;
+  } else {
+    smem = lds ? (size_t)c->S.n_tlet * 16 : (size_t)kStashQuads * block * 16;  // the treelet, or the world-ray stash (4 x 16 B per lane)
+    grid = persistent_grid(c, (const void*)f, smem, shared, block, 3, 4);
+  }
   hipLaunchKernelGGL(f, dim3(grid), dim3(block), smem, st, c->S, in, q.hits, q.ctrl, cur, c->d_cnt, tmin, tmax, t.trace);
   HIP_CHECK(hipGetLastError());
 }

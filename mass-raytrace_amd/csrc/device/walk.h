@@ -63,6 +63,14 @@ MRT_HD TRay tray_unstash(const TravIn& in) {
   r.a.b = e.y, r.a.y = e.z;
   return r;
 }
+// A path's stream (mrt_rng.h PathRng) as the pool keeps it: s0 and s1, low word first.
+MRT_HD PathRng rng_unpack(uint4 q) {
+  return PathRng{(unsigned long long)q.x | ((unsigned long long)q.y << 32),
+                 (unsigned long long)q.z | ((unsigned long long)q.w << 32)};
+}
+MRT_HD uint4 rng_pack(PathRng g) {
+  return make_uint4((uint32_t)g.s0, (uint32_t)(g.s0 >> 32), (uint32_t)g.s1, (uint32_t)(g.s1 >> 32));
+}
 
 // Inside a BLAS, `ret` is the world record after the instance/model record
 // that entered it, with kRetInstance set for an instance; the container of a
@@ -132,6 +140,27 @@ MRT_HD TRay world_ray(const TravIn& in, uint32_t ray) {
   const float4 o4 = in.ro[ray], d4 = in.rd[ray];
   return make_tray(V3{o4.x, o4.y, o4.z}, V3{d4.x, d4.y, d4.z}, in.S.fast_ok);
 }
+// Entering instance `id` (geom.rs:403-420): ray r through its inverse transform.
+MRT_HD TRay instance_ray(const DevScene& S, uint32_t id, const TRay& r) {
+  V3 c0, c1, c2, c3;
+  load_m12(S.inst_inv + (size_t)MRT_IDX(S, id, S.n_inst, 8) * 12, c0, c1, c2, c3);
+  return make_tray(xform(c0, c1, c2, c3, r.o, 1.0f), xform(c0, c1, c2, c3, r.d, 0.0f), S.fast_ok);
+}
+// Leaving one: the world ray again, from the lane's stash where it has one.
+MRT_HD TRay leave_instance(const TravIn& in, uint32_t ray) { return in.stash ? tray_unstash(in) : world_ray(in, ray); }
+// A box record's corners, a triangle record's vertex and edges (layout.h).
+struct RecBox {
+  V3 mn, mx;
+};
+MRT_HD RecBox rec_box(const uint4& s0, const uint4& s1) {
+  return {{u2f(s0.x), u2f(s0.y), u2f(s0.z)}, {u2f(s0.w), u2f(s1.x), u2f(s1.y)}};
+}
+struct RecTri {
+  V3 a, ab, ac;
+};
+MRT_HD RecTri rec_tri(const uint4& s0, const uint4& s1, const uint4& s2) {
+  return {{u2f(s0.x), u2f(s0.y), u2f(s0.z)}, {u2f(s0.w), u2f(s1.x), u2f(s1.y)}, {u2f(s2.x), u2f(s2.y), u2f(s2.z)}};
+}
 
 // Load record t.i. Every region ends in an END record (handled by
 // trav_prim: leave the BLAS, or finish), so there is no bounds compare here.
@@ -156,7 +185,7 @@ MRT_HD void trav_end_index(const TravIn& in, Trav& t) {
     t.done = true;
     return;
   }
-  if (t.ret & kRetInstance) t.r = in.stash ? tray_unstash(in) : world_ray(in, t.ray);
+  if (t.ret & kRetInstance) t.r = leave_instance(in, t.ray);
   t.i = t.ret & ~kRetInstance;
   t.ret = kNoRet;
 }
@@ -226,11 +255,7 @@ MRT_HD void nf_start(const TravIn& in, const NfStack& k, Trav& t) {
 // with the lane's stack (trav_init_nf).
 template <bool RNG, bool LDS, bool NF, bool WILD>
 MRT_HD void trav_begin(const TravIn& in, const NfStack& stk, Trav& t, uint32_t ray, float tmax, uint32_t start) {
-  if (RNG) {
-    const uint4 q = in.rng[ray];
-    t.rng = PathRng{(unsigned long long)q.x | ((unsigned long long)q.y << 32),
-                    (unsigned long long)q.z | ((unsigned long long)q.w << 32)};
-  }
+  if (RNG) t.rng = rng_unpack(in.rng[ray]);
   t.r = world_ray(in, ray);
   t.ray = ray;
   t.i = NF ? start : in.world_begin;  // the near-first walk starts at its own world tree
@@ -263,8 +288,8 @@ MRT_HD bool trav_at_box(const Trav& t) { return (int32_t)t.s1.w < 0; }  // kBoxF
 template <bool COUNT>
 MRT_HD void trav_box_index(const TravIn& in, Trav& t, LocalCounters& lc) {
   if (COUNT) lc.node_visits++;
-  V3 mn{u2f(t.s0.x), u2f(t.s0.y), u2f(t.s0.z)}, mx{u2f(t.s0.w), u2f(t.s1.x), u2f(t.s1.y)};
-  t.i = box_hit_any<COUNT>(mn, mx, t.r, in.tmin, t.best, &lc) ? (t.s1.w & ~kBoxFlag) : t.s1.z;
+  const RecBox b = rec_box(t.s0, t.s1);
+  t.i = box_hit_any<COUNT>(b.mn, b.mx, t.r, in.tmin, t.best, &lc) ? (t.s1.w & ~kBoxFlag) : t.s1.z;
 }
 template <bool COUNT, bool LDS = false>
 MRT_HD void trav_box(const TravIn& in, Trav& t, LocalCounters& lc) {
@@ -273,10 +298,7 @@ MRT_HD void trav_box(const TravIn& in, Trav& t, LocalCounters& lc) {
 }
 
 // The ray's RNG state back to the pool (RNG variants, when the ray is done).
-MRT_HD void trav_store_rng(const TravIn& in, const Trav& t) {
-  in.rng[t.ray] = make_uint4((uint32_t)t.rng.s0, (uint32_t)(t.rng.s0 >> 32), (uint32_t)t.rng.s1,
-                             (uint32_t)(t.rng.s1 >> 32));
-}
+MRT_HD void trav_store_rng(const TravIn& in, const Trav& t) { in.rng[t.ray] = rng_pack(t.rng); }
 
 // Volume::intersect once entry and exit of the target over the whole line are
 // known (geom.rs:623-653): both clipped to [tmin, best], then a distance
@@ -318,9 +340,9 @@ template <bool COUNT, uint32_t ALPHA, bool RNG, bool LDS>
 MRT_HD void trav_tri_index(const TravIn& in, Trav& t, LocalCounters& lc, uint4 s0, uint4 s1) {
   if (COUNT) lc.triangle_tests++;
   const uint4 s2 = rec_load1<LDS>(in, t.i + 2);
-  V3 a{u2f(s0.x), u2f(s0.y), u2f(s0.z)}, ab{u2f(s0.w), u2f(s1.x), u2f(s1.y)}, ac{u2f(s2.x), u2f(s2.y), u2f(s2.z)};
+  const RecTri v = rec_tri(s0, s1, s2);
   float th;
-  if (tri_hit(a, ab, ac, t.r.o, t.r.d, in.tmin, t.best, th)) {
+  if (tri_hit(v.a, v.ab, v.ac, t.r.o, t.r.d, in.tmin, t.best, th)) {
     const uint32_t id = s1.z & kTriIdMask;
     if (!ALPHA || !(s1.z & kTriAlpha) || tri_alpha_pass<RNG, ALPHA == 2>(in.S, id, t.r.o, t.r.d, th, t.rng, lc)) {
       t.best = th;
@@ -355,19 +377,20 @@ MRT_HD bool volume_hit_blas(const DevScene& S, const TravIn& in, Trav& t, LocalC
   const float best = t.best;
   const uint32_t prim = t.prim, hit_ret = t.hit_ret;
   if (inst) {
-    V3 c0, c1, c2, c3;
-    load_m12(S.inst_inv + (size_t)MRT_IDX(S, s0.y, S.n_inst, 8) * 12, c0, c1, c2, c3);
     if (in.stash) tray_stash(in, t.r);
-    t.r = make_tray(xform(c0, c1, c2, c3, t.r.o, 1.0f), xform(c0, c1, c2, c3, t.r.d, 0.0f), S.fast_ok);
+    t.r = instance_ray(S, s0.y, t.r);
   }
   TravIn vin = in;
   vin.tmin = -INFINITY;
   float te = 0.0f;
   bool second = false, hit = false;
-  if (COUNT) (inst ? lc.instance_entries : lc.model_entries)++;
-  t.i = s0.x;
-  t.best = INFINITY;
-  t.prim = kRefNone;
+  auto start_search = [&]() {
+    if (COUNT) (inst ? lc.instance_entries : lc.model_entries)++;
+    t.i = s0.x;
+    t.best = INFINITY;
+    t.prim = kRefNone;
+  };
+  start_search();
   for (;;) {
     trav_fetch<LDS>(vin, t);
     if (t.done) break;  // MRT_DEBUG_BOUNDS builds: the step cap
@@ -382,14 +405,11 @@ MRT_HD bool volume_hit_blas(const DevScene& S, const TravIn& in, Trav& t, LocalC
       second = true;
       te = t.best;
       vin.tmin = te + 0.0001f;
-      if (COUNT) (inst ? lc.instance_entries : lc.model_entries)++;
-      t.i = s0.x;
-      t.best = INFINITY;
-      t.prim = kRefNone;
+      start_search();
     }
   }
   const float tx = t.best;
-  if (inst) t.r = in.stash ? tray_unstash(in) : world_ray(in, t.ray);
+  if (inst) t.r = leave_instance(in, t.ray);
   t.best = best;
   t.prim = prim;
   t.hit_ret = hit_ret;
@@ -433,11 +453,9 @@ MRT_HD void trav_prim_index(const TravIn& in, Trav& t, LocalCounters& lc) {
     t.i = s1.y;
   } else if (kind == KIND_INST) {
     if (COUNT) lc.instance_entries++;
-    V3 c0, c1, c2, c3;
-    load_m12(S.inst_inv + (size_t)MRT_IDX(S, s0.x, S.n_inst, 8) * 12, c0, c1, c2, c3);
     // entered from the world region: t.r is the world ray here
     if (in.stash) tray_stash(in, t.r);
-    t.r = make_tray(xform(c0, c1, c2, c3, t.r.o, 1.0f), xform(c0, c1, c2, c3, t.r.d, 0.0f), S.fast_ok);
+    t.r = instance_ray(S, s0.x, t.r);
     t.ret = (t.i + 2) | kRetInstance;
     t.i = s0.y;
   } else {  // KIND_MODEL

@@ -114,7 +114,8 @@ MRT_HD void nf_over(Trav& t) {
 MRT_HD bool ref_box_hits(const TravIn& in, uint32_t rec, const TRay& r, float t) {
   uint4 a, b;
   rec_load2<false>(in, rec, a, b);
-  return box_hit_any(V3{u2f(a.x), u2f(a.y), u2f(a.z)}, V3{u2f(a.w), u2f(b.x), u2f(b.y)}, r, in.tmin, t);
+  const RecBox x = rec_box(a, b);
+  return box_hit_any(x.mn, x.mx, r, in.tmin, t);
 }
 
 // The near-first walk is over: does the reference's left-first walk reach
@@ -151,13 +152,7 @@ MRT_HD void nf_finish(const TravIn& in, Trav& t, LocalCounters& lc) {
       const uint32_t cid = ra.x, wpar = rb.x;
       if (wpar != kNoParent) ok = ref_box_hits(in, wpar, t.r, tau);
       if (ok && own != kNoParent) {
-        TRay r = t.r;
-        if (inst) {
-          V3 c0, c1, c2, c3;
-          load_m12(S.inst_inv + (size_t)MRT_IDX(S, cid, S.n_inst, 8) * 12, c0, c1, c2, c3);
-          r = make_tray(xform(c0, c1, c2, c3, t.r.o, 1.0f), xform(c0, c1, c2, c3, t.r.d, 0.0f), S.fast_ok);
-        }
-        ok = ref_box_hits(in, own, r, tau);
+        ok = ref_box_hits(in, own, inst ? instance_ray(S, cid, t.r) : t.r, tau);
       }
       if (COUNT) lc.node_visits += 1;
     }
@@ -315,10 +310,10 @@ MRT_HD void trav_prim_index_nf(const TravIn& in, const NfStack& k, Trav& t, Loca
   if (kind == KIND_TRI) {
     if (COUNT) lc.triangle_tests++;
     const uint4 s2 = rec_load1<false>(in, t.i + 2);
-    V3 a{u2f(s0.x), u2f(s0.y), u2f(s0.z)}, ab{u2f(s0.w), u2f(s1.x), u2f(s1.y)}, ac{u2f(s2.x), u2f(s2.y), u2f(s2.z)};
+    const RecTri v = rec_tri(s0, s1, s2);
     float th;
     // tested up to the culling bound: hits beyond `best` are recorded in t2
-    if (tri_hit_nb(a, ab, ac, t.r.o, t.r.d, in.tmin, nf_cull(t.best), th)) {
+    if (tri_hit_nb(v.a, v.ab, v.ac, t.r.o, t.r.d, in.tmin, nf_cull(t.best), th)) {
       const uint32_t id = s1.z & kTriIdMask;
       if (!ALPHA || !(s1.z & kTriAlpha) || tri_alpha_pass<false, ALPHA == 2>(S, id, t.r.o, t.r.d, th, t.rng, lc))
         nf_hit(in, t, th, make_ref(MRT_REF_TRIANGLE, id));
@@ -337,9 +332,7 @@ MRT_HD void trav_prim_index_nf(const TravIn& in, const NfStack& k, Trav& t, Loca
     nf_push(k, t, kNfRet);
     if (kind == KIND_INST) {
       if (COUNT) lc.instance_entries++;
-      V3 c0, c1, c2, c3;
-      load_m12(S.inst_inv + (size_t)MRT_IDX(S, s0.x, S.n_inst, 8) * 12, c0, c1, c2, c3);
-      t.r = make_tray(xform(c0, c1, c2, c3, t.r.o, 1.0f), xform(c0, c1, c2, c3, t.r.d, 0.0f), S.fast_ok);
+      t.r = instance_ray(S, s0.x, t.r);
       t.ret = (t.i + 2) | kRetInstance;
       nf_margin(in, t);  // the object space's margin
     } else {
@@ -352,5 +345,26 @@ MRT_HD void trav_prim_index_nf(const TravIn& in, const NfStack& k, Trav& t, Loca
   t.i = next;
   if (next == kNfPop && !nf_pop<WILD>(in, k, t)) nf_over(t);
 }
+
+// ---- the step a lane takes (k_trace; the host's replay in tools/slab_check.cpp) ----
+// NF: the kernel walks near-first, and only a lane that fell back (sp ==
+// kExactMode) takes the reference's steps; else every lane does.
+template <bool COUNT, bool NF, bool WILD>
+MRT_HD void trav_box_index_either(const TravIn& in, const NfStack& k, Trav& t, LocalCounters& lc) {
+  if (NF && t.sp != kExactMode)
+    trav_box_index_nf<COUNT, WILD>(in, k, t, lc);
+  else
+    trav_box_index<COUNT>(in, t, lc);
+}
+template <bool COUNT, uint32_t ALPHA, bool RNG, bool LDS, bool VBLAS, bool NF, bool WILD>
+MRT_HD void trav_prim_index_either(const TravIn& in, const NfStack& k, Trav& t, LocalCounters& lc) {
+  if (NF && t.sp != kExactMode)
+    trav_prim_index_nf<COUNT, ALPHA, WILD>(in, k, t, lc);
+  else
+    trav_prim_index<COUNT, ALPHA, RNG, LDS, VBLAS>(in, t, lc);
+}
+// the lane may fetch its next record: it is neither done nor waiting
+template <bool NF, bool WILD>
+MRT_HD bool trav_may_fetch(const Trav& t) { return !t.done && (!NF || !nf_parked<WILD>(t)); }
 
 }  // namespace mrt

@@ -249,22 +249,25 @@ void check_prim(const HostScene& s, const TravIn& in, const Trav& t, V wo, V wd)
   }
 }
 
-// One step of the reference walk and the fetch of the next record. st: the
-// record loads of the step by kind; check: the box and bound checks too.
-template <uint32_t ALPHA>
-void ref_step(const Scene& c, const TravIn& in, Trav& t, LocalCounters& lc, Stats* st, bool check, V wo, V wd) {
+// One step of the reference walk and the fetch of the next record, through
+// k_trace's own dispatch (walk_nf.h trav_*_either; NF, WILD: the kernel's
+// variant). st: the record loads of the step by kind; check: the box and
+// bound checks too.
+template <uint32_t ALPHA, bool NF = false, bool WILD = false>
+void ref_step(const Scene& c, const TravIn& in, const NfStack& stk, Trav& t, LocalCounters& lc, Stats* st, bool check,
+              V wo, V wd) {
   if (trav_at_box(t)) {
     if (st) st->loads += 2;
     if (st && check) check_box(in, t, *st);
-    trav_box_index<true>(in, t, lc);
+    trav_box_index_either<true, NF, WILD>(in, stk, t, lc);
   } else {
     const uint32_t kind = t.s1.w;
     if (st) st->loads += kind == KIND_TRI ? 3 : kind == KIND_INST ? 5 : 2;  // END, sphere, model: 2
     if (st && kind == KIND_INST) st->entries++;
     if (check && g_bc) check_prim(c.s, in, t, wo, wd);
-    trav_prim_index<true, ALPHA>(in, t, lc);
+    trav_prim_index_either<true, ALPHA, false, false, false, NF, WILD>(in, stk, t, lc);
   }
-  if (!t.done) trav_fetch(in, t);
+  if (trav_may_fetch<NF, WILD>(t)) trav_fetch(in, t);
 }
 
 // The reference's walk (k_trace's exact variant, one lane).
@@ -274,7 +277,7 @@ Hit walk_ref(const Scene& c, V o, V d, Stats* st = nullptr, bool check = false) 
   Trav t;
   LocalCounters lc;
   trav_init(p.in, t, 0, INFINITY);
-  while (!t.done) ref_step<ALPHA>(c, p.in, t, lc, st, check, o, d);
+  while (!t.done) ref_step<ALPHA>(c, p.in, NfStack{nullptr, 0}, t, lc, st, check, o, d);  // no stack: NF = false
   if (st) st->boxes += lc.node_visits, st->undecided += lc.box_exact;
   return trav_hit(p.in, t);
 }
@@ -297,7 +300,7 @@ Hit walk_nf_w(const Scene& c, V o, V d, Stats& st, uint64_t& fallbacks, uint64_t
   if (t.sp == kExactMode) ++starts_ref;  // nf_start: the bound does not cover this ray
   while (!t.done) {
     if (t.sp == kExactMode) {
-      ref_step<ALPHA>(c, in, t, lc, &st, false, o, d);
+      ref_step<ALPHA, true, WILD>(c, in, stk, t, lc, &st, false, o, d);
       continue;
     }
     if (WILD && t.sp == kNfWait) {  // k_trace sends a batch of such lanes into the wild tree; one lane is its own batch
@@ -315,7 +318,7 @@ Hit walk_nf_w(const Scene& c, V o, V d, Stats& st, uint64_t& fallbacks, uint64_t
     const bool in_inst = t.ret != kNoRet && (t.ret & kRetInstance);
     if (trav_at_box(t)) {
       st.loads += 2;
-      trav_box_index_nf<true, WILD>(in, stk, t, lc);
+      trav_box_index_either<true, true, WILD>(in, stk, t, lc);
     } else {
       const uint32_t kind = t.s1.w;
       if (kind == KIND_TRI || kind == KIND_SPHERE) {
@@ -330,14 +333,14 @@ Hit walk_nf_w(const Scene& c, V o, V d, Stats& st, uint64_t& fallbacks, uint64_t
         fprintf(stderr, "nf: unsupported kind %u at %u\n", kind, t.i);
         exit(2);
       }
-      trav_prim_index_nf<true, ALPHA, WILD>(in, stk, t, lc);
+      trav_prim_index_either<true, ALPHA, false, false, false, true, WILD>(in, stk, t, lc);
     }
     if (in_inst && t.ret == kNoRet) st.loads += 2;  // the step left an instance: the world ray again
     if (!nf_parked<WILD>(t) && t.sp > kNfStack - (WILD ? 0u : 1u)) {  // k_trace's LDS words per lane (launch_trace)
       fprintf(stderr, "nf: stack overflow\n");
       exit(3);
     }
-    if (!nf_parked<WILD>(t)) trav_fetch(in, t);
+    if (trav_may_fetch<true, WILD>(t)) trav_fetch(in, t);
   }
   st.boxes += lc.node_visits;
   fallbacks += lc.vnf_fallbacks;
