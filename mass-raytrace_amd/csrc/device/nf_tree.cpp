@@ -11,6 +11,7 @@
 // left-first walk reaches it, the smallest t with ties going to the later
 // primitive of its order — which a near-first walk of any tree finds — and
 // whether it reaches it is a property of the winner's ancestor boxes alone.
+// Records of either stream are read and written through records.h alone.
 #include <math.h>
 #include <cmath>
 #include <string.h>
@@ -18,42 +19,15 @@
 #include <algorithm>
 #include <unordered_map>
 
+#include "records.h"
 #include "upload.h"
 
 namespace mrt {
 
 namespace {
 
-float u2f(uint32_t u) {
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-uint32_t f2u(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  return u;
-}
-
-// ---- the reference stream (layout.h) ----
-uint32_t kind_of(const std::vector<uint32_t>& w, uint32_t i) { return w[4 * (i + 1) + 3]; }
-bool is_box(const std::vector<uint32_t>& w, uint32_t i) { return (kind_of(w, i) & kBoxFlag) != 0; }
-uint32_t skip_of(const std::vector<uint32_t>& w, uint32_t i) { return w[4 * (i + 1) + 2]; }
-uint32_t next_of(const std::vector<uint32_t>& w, uint32_t i) {
-  switch (kind_of(w, i)) {
-    case KIND_TRI: return w[4 * (i + 2) + 3];
-    case KIND_SPHERE:
-    case KIND_VOLUME: return w[4 * (i + 1) + 1];
-    default: return i + 2;  // instance / model: the record after it
-  }
-}
-// the items of a level: from `first` along successors until `end` (a skip
-// target) or an END record
-void level(const std::vector<uint32_t>& w, uint32_t first, uint32_t end, std::vector<uint32_t>& out) {
-  out.clear();
-  for (uint32_t c = first; c != end && kind_of(w, c) != KIND_END; c = is_box(w, c) ? skip_of(w, c) : next_of(w, c))
-    out.push_back(c);
-}
+using rec::f32;
+using rec::u32;
 
 struct Box {
   float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -280,11 +254,8 @@ struct Builder {
   std::vector<std::pair<uint32_t, uint32_t>> patches;  // (NF instance/model record, reference BLAS begin)
 
   uint32_t n_slots() const { return (uint32_t)(w.size() / 4); }
-  uint32_t push(uint32_t a, uint32_t b, uint32_t c, uint32_t dd) {
-    const uint32_t i = n_slots();
-    w.push_back(a), w.push_back(b), w.push_back(c), w.push_back(dd);
-    return i;
-  }
+  const uint32_t* ws() const { return w.data(); }  // the slot words as they stand (w grows)
+  uint32_t kind(uint32_t r) const { return rec::kind(ws(), r); }
 
   // Quantized frame of a node over its children's boxes a, b (layout.h NF
   // NODE): origin = the union's min, per axis the smallest step 2^e with
@@ -297,9 +268,9 @@ struct Builder {
   // costs at most 2^-15 of |origin| of range, never tightness.
   static float origin_with_byte(float v, uint8_t byte) {
     if (!(fabsf(v) >= 0x1p-100f)) v = fminf(v, -0x1p-100f);  // zero or tiny: a normal origin below it
-    uint32_t u = f2u(v), c = (u & ~0xFFu) | byte;
-    if (u2f(c) > v) c = v > 0.0f ? c - 0x100u : c + 0x100u;  // one step of 256 ulps further down
-    return u2f(c);
+    uint32_t u = u32(v), c = (u & ~0xFFu) | byte;
+    if (f32(c) > v) c = v > 0.0f ? c - 0x100u : c + 0x100u;  // one step of 256 ulps further down
+    return f32(c);
   }
   static bool quantize(const Box& a, const Box& b, const uint8_t cb[3], uint32_t o[3], uint32_t& ew, uint32_t q[3]) {
     uint8_t bytes[12];
@@ -309,7 +280,7 @@ struct Builder {
       const double hi = std::max((double)a.mx[k], (double)b.mx[k]);
       if (!(fabsf(mn) < INFINITY) || !(fabs(hi) < INFINITY)) return false;
       const float org = origin_with_byte(mn, cb[k]);
-      if (!(fabsf(org) < INFINITY) || !(org <= mn) || (f2u(org) & 0xFFu) != cb[k]) return false;
+      if (!(fabsf(org) < INFINITY) || !(org <= mn) || (u32(org) & 0xFFu) != cb[k]) return false;
       const double ext = hi - (double)org;
       int e = kNfExpMin;
       while (std::ldexp(254.0, e) < ext) ++e;
@@ -321,7 +292,7 @@ struct Builder {
       auto hi_q = [&](float v) {
         return (uint8_t)std::min(255.0, std::ceil(((double)v - org) / step + 0x1p-30));
       };
-      o[k] = f2u(org);
+      o[k] = u32(org);
       ew |= (uint32_t)(e + 127) << (8 * k);
       bytes[k] = lo_q(a.mn[k]);
       bytes[3 + k] = hi_q(a.mx[k]);
@@ -334,7 +305,7 @@ struct Builder {
     return true;
   }
 
-  uint32_t rec_slots(uint32_t r) const { return kind_of(w, r) == KIND_TRI ? 3u : 2u; }
+  uint32_t rec_slots(uint32_t r) const { return rec::n_slots(w.data(), r); }
   // slots of the record a child of a node starts with (a node, or its leaf's first object)
   uint32_t child_slots(const Tree& t, const Node& c) const { return c.l < 0 ? rec_slots(t.items[c.first].rec) : 2u; }
 
@@ -343,10 +314,7 @@ struct Builder {
     uint32_t pos = at;
     for (uint32_t k = 0; k < n.count; ++k) {
       const uint32_t r = t.items[n.first + k].rec;
-      if (k > 0) {
-        pos = n_slots();
-        for (uint32_t z = 0; z < 4 * rec_slots(r); ++z) w.push_back(0);
-      }
+      if (k > 0) pos = rec::grow(w, rec_slots(r));
       const uint32_t next = k + 1 == n.count ? kNfPop : std::max(n_slots(), pos + rec_slots(r));
       copy_record(r, pos, next);
     }
@@ -356,14 +324,11 @@ struct Builder {
   bool emit_node(const Tree& t, const Node& n, uint32_t at) {
     const Node& L = t.nodes[n.l];
     const Node& R = t.nodes[n.r];
-    const uint32_t lsz = child_slots(t, L), rsz = child_slots(t, R), base = n_slots();
-    for (uint32_t z = 0; z < 4 * (lsz + rsz); ++z) w.push_back(0);
+    const uint32_t lsz = child_slots(t, L), rsz = child_slots(t, R), base = rec::grow(w, lsz + rsz);
     uint32_t o[3], ew, q[3];
     if (!quantize(L.b, R.b, n.cb, o, ew, q)) return false;
     if (lsz < 2 || lsz > 3) return false;  // a node (2 slots) or a leaf's first record (2 or 3)
-    uint32_t* rec = &w[4 * (size_t)at];
-    rec[0] = o[0], rec[1] = o[1], rec[2] = o[2], rec[3] = ew | (lsz - 2) << 24 | (uint32_t)n.code << 25;
-    rec[4] = q[0], rec[5] = q[1], rec[6] = q[2], rec[7] = kBoxFlag | n.force | base;
+    rec::put_nf_node(w.data(), at, o, ew, q, lsz, n.code, n.force, base);
     s.nf_boxes++;
     for (const auto& [c, pos] : {std::pair<const Node*, uint32_t>{&L, base}, {&R, base + lsz}}) {
       if (c->l < 0)
@@ -377,9 +342,7 @@ struct Builder {
   // ~0u when a box cannot be quantized
   uint32_t emit(const Tree& t) {
     const Node& root = t.nodes[0];
-    const uint32_t at = n_slots();
-    const uint32_t sz = child_slots(t, root);
-    for (uint32_t z = 0; z < 4 * sz; ++z) w.push_back(0);
+    const uint32_t at = rec::grow(w, child_slots(t, root));
     if (root.l < 0) {
       emit_leaf(t, root, at);
       return at;
@@ -388,26 +351,21 @@ struct Builder {
   }
   // reference record `r` copied to slot `at` with the leaf's successor `next`
   void copy_record(uint32_t r, uint32_t at, uint32_t next) {
-    const uint32_t k = kind_of(w, r);
-    for (uint32_t q = 0; q < 4 * rec_slots(r); ++q) w[4 * (size_t)at + q] = w[4 * (size_t)r + q];
-    switch (k) {
-      case KIND_TRI: w[4 * (at + 2) + 3] = next; break;
-      case KIND_SPHERE: w[4 * (at + 1) + 1] = next; break;
-      case KIND_INST:
-      case KIND_MODEL:
-        w[4 * at + 2] = next;
-        w[4 * (at + 1)] = s.vnf_leaf[2 * (size_t)vnf_slot(r)];  // its reference world parent (walk_nf.h nf_finish)
-        patches.push_back({at, w[4 * r + 1]});  // the reference BLAS region it enters
-        if (wild_term.count(r)) wild_at.push_back({at, r});
-        break;
-      default: break;
+    uint32_t* v = w.data();
+    rec::copy(rec::at(v, at), v, r);
+    const uint32_t k = rec::kind(v, r);
+    if (k == KIND_INST || k == KIND_MODEL) {
+      rec::set_nf_parent(v, at, s.vnf_leaf[2 * (size_t)vnf_slot(r)]);  // its reference world parent (walk_nf.h nf_finish)
+      patches.push_back({at, rec::blas_begin(v, r)});  // the reference BLAS region it enters
+      if (wild_term.count(r)) wild_at.push_back({at, r});
     }
+    rec::set_nf_next(v, at, next);
   }
 
   // reference parents and keys of the objects of a region (left-first order)
   bool ref_order(uint32_t first, bool world, std::vector<uint32_t>& objects) {
     std::vector<uint32_t> kids, top;
-    level(w, first, ~0u, top);
+    rec::level(ws(), first, ~0u, top);
     struct F {
       uint32_t rec, parent;
     };
@@ -417,22 +375,17 @@ struct Builder {
     while (!st.empty()) {
       const F f = st.back();
       st.pop_back();
-      if (is_box(w, f.rec)) {
-        level(w, kind_of(w, f.rec) & ~kBoxFlag, skip_of(w, f.rec), kids);
+      if (rec::is_box(ws(), f.rec)) {
+        rec::box_children(ws(), f.rec, kids);
         for (size_t k = kids.size(); k-- > 0;) st.push_back({kids[k], f.rec});
         continue;
       }
-      const uint32_t kd = kind_of(w, f.rec);
-      uint32_t slot;
-      switch (kd) {
-        case KIND_SPHERE: slot = s.vnf_base[VNF_SPHERE] + w[4 * (f.rec + 1)]; break;
-        case KIND_TRI: slot = s.vnf_base[VNF_TRI] + (w[4 * (f.rec + 1) + 2] & kTriIdMask); break;
-        case KIND_INST: slot = s.vnf_base[VNF_INST] + w[4 * f.rec]; break;
-        case KIND_MODEL: slot = s.vnf_base[VNF_MODEL] + w[4 * f.rec]; break;
-        default:
-          s.nf_note = "a volume in the world";
-          return false;
+      const uint32_t kd = kind(f.rec);
+      if (kd != KIND_SPHERE && kd != KIND_TRI && kd != KIND_INST && kd != KIND_MODEL) {
+        s.nf_note = "a volume in the world";
+        return false;
       }
+      const uint32_t slot = vnf_slot(f.rec);
       if (s.vnf_leaf[2 * slot] != 0xFFFFFFFEu) {
         s.nf_note = "an object referenced twice";
         return false;
@@ -476,21 +429,24 @@ struct Builder {
   // is the walk's margin, nf_bound.h).
   Box object_box(uint32_t r, TriBound* tb) {
     Box b;
-    const uint32_t* q = &w[4 * (size_t)r];
-    switch (kind_of(w, r)) {
+    const uint32_t* v = ws();
+    switch (kind(r)) {
       case KIND_SPHERE: {
         // the ball, plus the bound's terms proportional to the radius (90.2u |r|)
-        const double rad = std::fabs((double)u2f(q[3])) * (1.0 + 0x1p-17);
-        for (int k = 0; k < 3; ++k) b.mn[k] = f_down(u2f(q[k]) - rad), b.mx[k] = f_up(u2f(q[k]) + rad);
+        float c[3];
+        rec::sphere_center(v, r, c);
+        const double rad = std::fabs((double)rec::sphere_radius(v, r)) * (1.0 + 0x1p-17);
+        for (int k = 0; k < 3; ++k) b.mn[k] = f_down(c[k] - rad), b.mx[k] = f_up(c[k] + rad);
         pad_box(b, 0.0f);
         break;
       }
       case KIND_TRI: {
-        const mrt_triangle& t = d.triangles[q[6] & kTriIdMask];
+        const mrt_triangle& t = d.triangles[rec::tri_id(v, r)];
         b.grow(t.a[0], t.a[1], t.a[2]);
         b.grow(t.b[0], t.b[1], t.b[2]);
         b.grow(t.c[0], t.c[1], t.c[2]);
-        const float ab[3] = {u2f(q[3]), u2f(q[4]), u2f(q[5])}, ac[3] = {u2f(q[8]), u2f(q[9]), u2f(q[10])};
+        float ab[3], ac[3];
+        rec::tri_ab(v, r, ab), rec::tri_ac(v, r, ac);
         const TriBound tbd = tri_bound(ab, ac);
         if (tb) grow_bound(*tb, tbd);
         if (tbd.a1 > 0) gen_extent.push_back(std::max(b.mx[0] - b.mn[0], std::max(b.mx[1] - b.mn[1], b.mx[2] - b.mn[2])));
@@ -500,20 +456,20 @@ struct Builder {
       }
       case KIND_INST:
       case KIND_MODEL: {
-        auto it = region_of.find(q[1]);  // the reference BLAS region it enters
+        auto it = region_of.find(rec::blas_begin(v, r));  // the reference BLAS region it enters
         if (it == region_of.end()) {
           b.grow(-INFINITY, -INFINITY, -INFINITY);
           b.grow(INFINITY, INFINITY, INFINITY);
           break;
         }
         const Box& ob = blas_box[it->second];
-        if (kind_of(w, r) == KIND_MODEL) {
+        if (kind(r) == KIND_MODEL) {
           b = ob;
           break;
         }
         // the hull of the transformed corners, in double (each product of
         // two floats exact, the sum's rounding added) and rounded outward
-        const float* f = d.instances[q[0]].fwd;  // column-major 4x4 (M4::transform)
+        const float* f = d.instances[rec::object_id(v, r)].fwd;  // column-major 4x4 (M4::transform)
         for (int c = 0; c < 8; ++c) {
           const double x = c & 1 ? ob.mx[0] : ob.mn[0], y = c & 2 ? ob.mx[1] : ob.mn[1], z = c & 4 ? ob.mx[2] : ob.mn[2];
           for (int k = 0; k < 3; ++k) {
@@ -572,15 +528,7 @@ struct Builder {
   static bool wild(const InstTerm& m) { return m.w0 > 0x1p-14 || m.w1 > 0x1p-14 || m.b1 > 0x1p-14; }
 
   // vnf_leaf slot of a leaf object's record
-  uint32_t vnf_slot(uint32_t r) const {
-    const uint32_t* q = &w[4 * (size_t)r];
-    switch (kind_of(w, r)) {
-      case KIND_SPHERE: return s.vnf_base[VNF_SPHERE] + q[4];
-      case KIND_TRI: return s.vnf_base[VNF_TRI] + (q[6] & kTriIdMask);
-      case KIND_INST: return s.vnf_base[VNF_INST] + q[0];
-      default: return s.vnf_base[VNF_MODEL] + q[0];
-    }
-  }
+  uint32_t vnf_slot(uint32_t r) const { return rec::vnf_slot(ws(), r, s.vnf_base); }
   void keep_box(uint32_t r, const Box& b) {
     if (!s.keep_nf_boxes) return;
     float* p = &s.nf_leaf_box[6 * (size_t)vnf_slot(r)];
@@ -606,10 +554,10 @@ struct Builder {
       const uint32_t r = t.items[i].rec;
       N& x = it[i];
       x.kind = 0;
-      const uint32_t kd = kind_of(w, r);
+      const uint32_t kd = kind(r);
       if (kd == KIND_TRI) {
-        const float ab[3] = {u2f(w[4 * (size_t)r + 3]), u2f(w[4 * (size_t)r + 4]), u2f(w[4 * (size_t)r + 5])};
-        const float ac[3] = {u2f(w[4 * (size_t)r + 8]), u2f(w[4 * (size_t)r + 9]), u2f(w[4 * (size_t)r + 10])};
+        float ab[3], ac[3];
+        rec::tri_ab(ws(), r, ab), rec::tri_ac(ws(), r, ac);
         if (!(tri_bound(ab, ac).a1 > 0)) continue;
         // N = ab x ac: each product of two floats exact in double, one rounding per component
         const double nn[3] = {(double)ab[1] * ac[2] - (double)ab[2] * ac[1], (double)ab[2] * ac[0] - (double)ab[0] * ac[2],
@@ -622,7 +570,7 @@ struct Builder {
         for (int k = 0; k < 3; ++k) x.n[k] = nn[k] / ln;
         x.m = norm3(dab) * norm3(dac) / ln * (1.0 + 1e-9);
       } else if (kd == KIND_INST || kd == KIND_MODEL) {
-        auto rg = region_of.find(w[4 * (size_t)r + 1]);
+        auto rg = region_of.find(rec::blas_begin(ws(), r));
         if (rg != region_of.end() && blas_bound[rg->second].a1 > 0) x.kind = 2;
       }
     }
@@ -721,9 +669,9 @@ struct Builder {
     // which BLAS regions models / instances enter (world objects)
     std::vector<uint8_t> by_model(s.blas_regions.size(), 0), by_inst(s.blas_regions.size(), 0);
     for (uint32_t r : world_objs) {
-      const uint32_t kd = kind_of(w, r);
+      const uint32_t kd = kind(r);
       if (kd != KIND_INST && kd != KIND_MODEL) continue;
-      auto it = region_of.find(w[4 * (size_t)r + 1]);
+      auto it = region_of.find(rec::blas_begin(ws(), r));
       if (it != region_of.end()) (kd == KIND_MODEL ? by_model : by_inst)[it->second] = 1;
     }
     // trees; stack entries the walk may need: a far child per internal level
@@ -765,30 +713,32 @@ struct Builder {
     // primitives' trees (mesh_ply's 1M triangles of 0.01), while a wild
     // instance costs one box test of its own where the walk reaches it
     uint32_t n_world_inst = 0;
-    for (uint32_t r : world_objs) n_world_inst += kind_of(w, r) == KIND_INST;
+    for (uint32_t r : world_objs) n_world_inst += kind(r) == KIND_INST;
     const bool few = n_world_inst <= kNfWildFew;
     for (uint32_t r : world_objs) {
-      const uint32_t kd = kind_of(w, r);
+      const uint32_t kd = kind(r);
       TriBound tb;
       const Box b = object_box(r, kd == KIND_TRI ? &tb : nullptr);
       keep_box(r, b);
       if (kd == KIND_TRI) grow_bound(world_tri, tb);
       bool generic = tb.a1 > 0;
       if (kd == KIND_INST || kd == KIND_MODEL) {
-        auto it = region_of.find(w[4 * (size_t)r + 1]);
+        auto it = region_of.find(rec::blas_begin(ws(), r));
         generic = it != region_of.end() && blas_bound[it->second].a1 > 0;
       }
       if (kd == KIND_SPHERE) {
-        const double rad = std::fabs((double)u2f(w[4 * (size_t)r + 3]));
+        float c[3];
+        rec::sphere_center(ws(), r, c);
+        const double rad = std::fabs((double)rec::sphere_radius(ws(), r));
         r_min = std::min(r_min, rad), r_max = std::max(r_max, rad);
         Box sb;
-        for (int k = 0; k < 3; ++k) sb.mn[k] = f_down(u2f(w[4 * (size_t)r + k]) - rad), sb.mx[k] = f_up(u2f(w[4 * (size_t)r + k]) + rad);
+        for (int k = 0; k < 3; ++k) sb.mn[k] = f_down(c[k] - rad), sb.mx[k] = f_up(c[k] + rad);
         sph_box.grow(sb);
       }
       if (kd == KIND_INST) {
-        auto it = region_of.find(w[4 * (size_t)r + 1]);
+        auto it = region_of.find(rec::blas_begin(ws(), r));
         const TriBound ob = it == region_of.end() ? TriBound{} : blas_bound[it->second];
-        const InstTerm m = inst_term(w[4 * (size_t)r], ob);
+        const InstTerm m = inst_term(rec::object_id(ws(), r), ob);
         ko1 = std::max(ko1, m.ko);
         if (it != region_of.end()) {
           const Box& bb = blas_box[it->second];
@@ -802,7 +752,7 @@ struct Builder {
           wild_items.push_back({b, r, true});
           wild_term[r] = {b, m};
           s.nf_wild++;
-          if (s.keep_nf_boxes) s.nf_inst_wild[w[4 * (size_t)r]] = 1;
+          if (s.keep_nf_boxes) s.nf_inst_wild[rec::object_id(ws(), r)] = 1;
           continue;
         }
         aw0 = std::max(aw0, m.w0), aw1 = std::max(aw1, m.w1), bw0 = std::max(bw0, m.b0), bw1 = std::max(bw1, m.b1);
@@ -825,7 +775,7 @@ struct Builder {
     // and instances cost the world tree a leaf test each.
     Tree wild_tree;
     bool has_model = false;
-    for (const Item& it : items) has_model = has_model || kind_of(w, it.rec) == KIND_MODEL;
+    for (const Item& it : items) has_model = has_model || kind(it.rec) == KIND_MODEL;
     const bool split = !wild_items.empty() && !items.empty() && !has_model;
     const uint32_t below = has_blas ? 2 + blas_depth : 0;
     world.items = items;
@@ -916,16 +866,15 @@ struct Builder {
       if (!finite) continue;  // no entry: the instance is entered whenever its forced path is walked
       float c[3], rr;
       ball(b, c, rr);
-      const uint32_t e = push(f2u(b.mn[0]), f2u(b.mn[1]), f2u(b.mn[2]), f2u(b.mx[0]));
-      push(f2u(b.mx[1]), f2u(b.mx[2]), f2u(f_up(m.w0)), f2u(f_up(m.w1)));
-      push(f2u(f_up(m.b0 + 0x1p-90)), f2u(f_up(m.b1)), f2u(c[0]), f2u(c[1]));
-      push(f2u(c[2]), f2u(rr), 0, 0);
-      w[4 * (size_t)at + 3] = e;
+      const NfWild e{{b.mn[0], b.mn[1], b.mn[2]}, {b.mx[0], b.mx[1], b.mx[2]}, f_up(m.w0), f_up(m.w1),
+                     f_up(m.b0 + 0x1p-90), f_up(m.b1), {c[0], c[1], c[2]}, rr};
+      const uint32_t entry = rec::put_nf_wild(w, e);
+      rec::set_nf_wild(w.data(), at, entry);
     }
-    for (auto& [rec, ref_blas] : patches) {
+    for (auto& [leaf, ref_blas] : patches) {
       auto it = blas_root.find(ref_blas);
       if (it == blas_root.end()) return (s.nf_note = "an instance of an empty BLAS", true);
-      w[4 * rec + 1] = it->second;
+      rec::set_nf_blas_root(w.data(), leaf, it->second);
     }
     if (n_slots() > kNfIdx) return (s.nf_note = "record stream past 2^28 slots", true);
     s.nf_ok = true;

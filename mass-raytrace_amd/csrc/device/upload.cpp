@@ -1,4 +1,6 @@
-// upload.cpp — linearise the reference BVH into the preorder slot stream.
+// upload.cpp — linearise the reference BVH into the preorder slot stream,
+// relay its BLAS regions with siblings together, choose the LDS treelet.
+// Records are read, written and patched through records.h alone.
 #include "upload.h"
 
 #include <math.h>
@@ -10,15 +12,11 @@
 #include <stdexcept>
 #include <unordered_map>
 
+#include "records.h"
+
 namespace mrt {
 
 namespace {
-
-uint32_t fbits(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  return u;
-}
 
 // Surfaces -> GpuSurfRef; composites become postfix programs (layout.h).
 struct SurfResolver {
@@ -147,19 +145,12 @@ struct Emitter {
   std::vector<std::pair<uint32_t, uint32_t>> jump_patches;  // (slot index, blas root node)
 
   uint32_t n_slots() const { return (uint32_t)(s.slots.size() / 4); }
-  uint32_t push_slot(uint32_t a, uint32_t b, uint32_t c, uint32_t w) {
-    uint32_t i = n_slots();
-    s.slots.push_back(a), s.slots.push_back(b), s.slots.push_back(c), s.slots.push_back(w);
-    return i;
-  }
 
   // END record closing a region (world or BLAS): a box skip or the last
   // primitive of the region lands on it, so the device never compares the
   // record index against the region's end.
   void push_end() {
-    s.rec_starts.push_back(n_slots());
-    push_slot(0, 0, 0, 0);
-    push_slot(0, 0, 0, KIND_END);
+    s.rec_starts.push_back(rec::put_end(s.slots));
   }
 
   bool emit_prim(uint32_t ref, bool in_blas) {
@@ -169,8 +160,7 @@ struct Emitter {
       case MRT_REF_SPHERE: {
         if (idx >= d.n_spheres) return fail("sphere index out of range");
         const mrt_sphere& sp = d.spheres[idx];
-        const uint32_t at = push_slot(fbits(sp.center[0]), fbits(sp.center[1]), fbits(sp.center[2]), fbits(sp.radius));
-        push_slot(idx, at + 2, 0, KIND_SPHERE);  // next: the following record
+        rec::put_sphere(s.slots, sp.center, sp.radius, idx);
         s.n_prim_records++;
         return true;
       }
@@ -185,9 +175,7 @@ struct Emitter {
           id |= kTriAlpha;
           s.has_alpha = true;
         }
-        const uint32_t at = push_slot(fbits(t.a[0]), fbits(t.a[1]), fbits(t.a[2]), fbits(ab[0]));
-        push_slot(fbits(ab[1]), fbits(ab[2]), id, KIND_TRI);
-        push_slot(fbits(ac[0]), fbits(ac[1]), fbits(ac[2]), at + 3);  // next: the following record
+        rec::put_tri(s.slots, t.a, ab, ac, id);
         s.n_prim_records++;
         return true;
       }
@@ -201,15 +189,12 @@ struct Emitter {
           const uint32_t ti = MRT_REF_INDEX(tr);
           const uint32_t root = inst ? d.instances[ti].blas_root : d.models[ti].blas_root;
           if (root >= d.n_nodes) return fail("BLAS root out of range");
-          const uint32_t at = push_slot(0, ti, 0, 0);
-          push_slot(idx, at + 2, inst ? kVolInstance : kVolModel, KIND_VOLUME);
-          volume_patches.push_back({at, root});
+          volume_patches.push_back({rec::put_volume_blas(s.slots, idx, inst ? kVolInstance : kVolModel, ti), root});
           s.vol_blas = true;
           return true;
         }
         const mrt_volume& v = d.volumes[idx];
-        const uint32_t at = push_slot(fbits(v.center[0]), fbits(v.center[1]), fbits(v.center[2]), fbits(v.radius));
-        push_slot(idx, at + 2, 0, KIND_VOLUME);
+        rec::put_volume_sphere(s.slots, v.center, v.radius, idx);
         return true;
       }
       case MRT_REF_INSTANCE:
@@ -224,9 +209,7 @@ struct Emitter {
           root = d.models[idx].blas_root;
         }
         if (root >= d.n_nodes) return fail("BLAS root out of range");
-        uint32_t at = push_slot(idx, 0, 0, 0);
-        push_slot(0, 0, 0, kind == MRT_REF_INSTANCE ? KIND_INST : KIND_MODEL);
-        jump_patches.push_back({at, root});
+        jump_patches.push_back({rec::put_inst_or_model(s.slots, kind == MRT_REF_INSTANCE ? KIND_INST : KIND_MODEL, idx), root});
         s.n_prim_records++;
         return true;
       }
@@ -272,7 +255,7 @@ struct Emitter {
       Frame f = stack.back();
       stack.pop_back();
       if (f.box_slot != ~0u) {
-        s.slots[4 * (f.box_slot + 1) + 2] = n_slots();  // skip = first slot after subtree
+        rec::set_box_skip(s.slots.data(), f.box_slot, n_slots());  // skip = first slot after subtree
         continue;
       }
       if (MRT_REF_KIND(f.ref) != MRT_REF_NODE) {
@@ -291,9 +274,8 @@ struct Emitter {
           if (!(a <= 0x1p28f)) s.early_ok = 0;  // NaN and inf too
         }
       }
-      s.rec_starts.push_back(n_slots());
-      uint32_t at = push_slot(fbits(n.min[0]), fbits(n.min[1]), fbits(n.min[2]), fbits(n.max[0]));
-      push_slot(fbits(n.max[1]), fbits(n.max[2]), 0, kBoxFlag | (at + 2));  // hit: the first child, next
+      const uint32_t at = rec::put_box(s.slots, n.min, n.max);  // hit: the first child, next
+      s.rec_starts.push_back(at);
       s.n_box_records++;
       stack.push_back({0, at});  // closes after both children
       if (MRT_REF_KIND(n.right) != MRT_REF_NONE) stack.push_back({n.right, ~0u});
@@ -304,31 +286,6 @@ struct Emitter {
     return true;
   }
 };
-
-// ---- record helpers (layout.h) ----
-uint32_t rec_kind(const std::vector<uint32_t>& w, uint32_t i) { return w[4 * (i + 1) + 3]; }
-bool rec_is_box(const std::vector<uint32_t>& w, uint32_t i) { return (rec_kind(w, i) & kBoxFlag) != 0; }
-uint32_t rec_slots(const std::vector<uint32_t>& w, uint32_t i) {
-  const uint32_t k = rec_kind(w, i);
-  return (k & kBoxFlag) ? 2 : (k == KIND_TRI ? 3 : 2);
-}
-// the record the traversal reaches after primitive / instance record i
-uint32_t rec_next(const std::vector<uint32_t>& w, uint32_t i) {
-  switch (rec_kind(w, i)) {
-    case KIND_TRI: return w[4 * (i + 2) + 3];
-    case KIND_SPHERE:
-    case KIND_VOLUME: return w[4 * (i + 1) + 1];
-    default: return i + 2;  // instance / model: the record after it
-  }
-}
-// children of box record i, in order (the first is its hit index; a child's
-// successor at its level: a box's skip, a primitive's next)
-void box_children(const std::vector<uint32_t>& w, uint32_t i, std::vector<uint32_t>& out) {
-  out.clear();
-  const uint32_t end = w[4 * (i + 1) + 2];
-  for (uint32_t c = rec_kind(w, i) & ~kBoxFlag; c != end; c = rec_is_box(w, c) ? w[4 * (c + 1) + 2] : rec_next(w, c))
-    out.push_back(c);
-}
 
 // Regions laid out with siblings together (round 3): the
 // region's top-level items first, then every box's children as one group,
@@ -348,14 +305,14 @@ void box_children(const std::vector<uint32_t>& w, uint32_t i, std::vector<uint32
 // cube_field unchanged, Menger 38.1 -> 31.4 Msamples/s (the instance pairs of
 // its leaves end up beside their successors' groups, not their parents').
 struct Relayout {
-  const std::vector<uint32_t>& w;
+  const uint32_t* w;
   std::vector<uint32_t>& out;
   std::vector<uint32_t>& remap;
   uint32_t at = 0;
 
   void place(uint32_t r) {
     remap[r] = at;
-    at += rec_slots(w, r);
+    at += rec::n_slots(w, r);
   }
   void group(const std::vector<uint32_t>& g, uint32_t align) {
     at = (at + align - 1) / align * align;
@@ -366,75 +323,59 @@ struct Relayout {
   // without instance / model records
   void region(uint32_t begin, uint32_t end_rec) {
     std::vector<uint32_t> top, kids;
-    for (uint32_t j = begin; j != end_rec; j = rec_is_box(w, j) ? w[4 * (j + 1) + 2] : rec_next(w, j)) top.push_back(j);
+    rec::level(w, begin, end_rec, top);
     std::vector<uint32_t> stack(top.rbegin(), top.rend());
     std::vector<uint32_t> boxes;  // DFS order
     while (!stack.empty()) {
       const uint32_t r = stack.back();
       stack.pop_back();
-      if (rec_kind(w, r) == KIND_INST || rec_kind(w, r) == KIND_MODEL)
+      if (rec::kind(w, r) == KIND_INST || rec::kind(w, r) == KIND_MODEL)
         throw std::logic_error("relayout: an instance inside a relaid region");
-      if (!rec_is_box(w, r)) continue;
+      if (!rec::is_box(w, r)) continue;
       boxes.push_back(r);
-      box_children(w, r, kids);
+      rec::box_children(w, r, kids);
       for (size_t k = kids.size(); k-- > 0;) stack.push_back(kids[k]);
     }
     at = (at + 7) & ~7u;  // the region on a 128-B line
     group(top, 4);
     for (uint32_t b : boxes) {
-      box_children(w, b, kids);
+      rec::box_children(w, b, kids);
       bool any_box = false;
-      for (uint32_t c : kids) any_box |= rec_is_box(w, c);
+      for (uint32_t c : kids) any_box |= rec::is_box(w, c);
       group(kids, any_box ? 4 : 2);
     }
     at = (at + 1) & ~1u;
     place(end_rec);
   }
 
-  // copy every placed record of `recs` with its successor indices remapped
+  // copy every placed record of `recs` with each index it holds remapped
+  // (successors, an instance's or model's BLAS range, a volume target's BLAS)
   void emit(const std::vector<uint32_t>& recs) {
     out.resize(4 * (size_t)at, 0u);
     for (uint32_t o : recs) {
-      const uint32_t n = remap[o], sl = rec_slots(w, o);
-      std::copy(w.begin() + 4 * (size_t)o, w.begin() + 4 * (size_t)(o + sl), out.begin() + 4 * (size_t)n);
-      uint32_t* rec = &out[4 * (size_t)n];
-      const uint32_t k = rec_kind(w, o);
-      if (k & kBoxFlag) {
-        rec[6] = remap[rec[6]];
-        rec[7] = kBoxFlag | remap[rec[7] & ~kBoxFlag];
-      } else if (k == KIND_TRI) {
-        rec[11] = remap[rec[11]];
-      } else if (k == KIND_SPHERE || k == KIND_VOLUME) {
-        rec[5] = remap[rec[5]];
-      }
+      uint32_t* r = rec::at(out.data(), remap[o]);
+      rec::copy(r, w, o);
+      rec::for_each_link(r, [&](uint32_t& index, rec::LinkKind) { index = remap[index]; });
     }
   }
 };
 
 void relayout(HostScene& s) {
-  const std::vector<uint32_t>& w = s.slots;
-  std::vector<uint32_t> out, remap(w.size() / 4, ~0u);
+  const uint32_t* w = s.slots.data();
+  std::vector<uint32_t> out, remap(s.slots.size() / 4, ~0u);
   Relayout L{w, out, remap, 0};
   // the world region (emitted first) as it is
   uint32_t wend = s.world_end + 2;
   for (uint32_t i : s.rec_starts)
     if (i < wend) L.place(i);
   for (const BlasRegion& r : s.blas_regions) L.region(r.begin, r.end);
-  for (uint32_t i : s.rec_starts)
+  for (uint32_t i : s.rec_starts) {
     if (remap[i] == ~0u) throw std::logic_error("relayout: a record was not placed");
-  L.emit(s.rec_starts);
-  for (uint32_t i : s.rec_starts) {  // instance / model records: their BLAS ranges
-    const uint32_t k = rec_kind(w, i);
-    if (k == KIND_INST || k == KIND_MODEL) {
-      uint32_t* rec = &out[4 * (size_t)remap[i]];
-      rec[1] = remap[rec[1]];
-      rec[2] = remap[rec[2]];
-      if (remap[i + 2] != remap[i] + 2) throw std::logic_error("relayout: an instance moved away from its successor");
-    } else if (k == KIND_VOLUME && w[4 * (i + 1) + 2]) {  // its target's BLAS
-      uint32_t* rec = &out[4 * (size_t)remap[i]];
-      rec[0] = remap[rec[0]];
-    }
+    const uint32_t k = rec::kind(w, i);
+    if ((k == KIND_INST || k == KIND_MODEL) && remap[i + 2] != remap[i] + 2)
+      throw std::logic_error("relayout: an instance moved away from its successor");
   }
+  L.emit(s.rec_starts);
   s.world_begin = remap[s.world_begin];
   s.world_end = remap[s.world_end];
   for (BlasRegion& r : s.blas_regions) r.begin = remap[r.begin], r.end = remap[r.end];
@@ -619,41 +560,39 @@ bool build_host_scene(const mrt_scene_desc& d, HostScene& s, std::string& err, b
   e.push_end();
   // BLAS regions, one per distinct root, emitted once and shared
   std::unordered_map<uint32_t, size_t> blas;  // BLAS root node -> s.blas_regions index
-  for (auto& p : e.jump_patches) {
-    auto it = blas.find(p.second);
+  // the region of BLAS root node `root`, emitted on its first use; null: emission failed
+  auto region_of = [&](uint32_t root) -> BlasRegion* {
+    auto it = blas.find(root);
     if (it == blas.end()) {
       uint32_t b = e.n_slots();
-      if (!e.emit_tree(MRT_REF(MRT_REF_NODE, p.second), true)) return false;
+      if (!e.emit_tree(MRT_REF(MRT_REF_NODE, root), true)) return nullptr;
       s.blas_regions.push_back({b, e.n_slots(), 0, false});
-      it = blas.emplace(p.second, s.blas_regions.size() - 1).first;
+      it = blas.emplace(root, s.blas_regions.size() - 1).first;
       e.push_end();
     }
-    BlasRegion& r = s.blas_regions[it->second];
-    r.refs++;
-    if (s.slots[4 * (p.first + 1) + 3] == KIND_MODEL) r.model = true;
-    s.slots[4 * p.first + 1] = r.begin;
-    s.slots[4 * p.first + 2] = r.end;
+    return &s.blas_regions[it->second];
+  };
+  for (auto& p : e.jump_patches) {
+    BlasRegion* r = region_of(p.second);
+    if (!r) return false;
+    r->refs++;
+    if (rec::kind(s.slots.data(), p.first) == KIND_MODEL) r->model = true;
+    rec::set_blas_range(s.slots.data(), p.first, r->begin, r->end);
   }
   // the targets of volumes: the same regions, shared with the instances and
   // models of the same BLAS. The nested searches (walk.h volume_hit_blas) step
   // boxes and triangles and end on the END record: nothing else may be there.
   for (auto& p : e.volume_patches) {
-    auto it = blas.find(p.second);
-    if (it == blas.end()) {
-      uint32_t b = e.n_slots();
-      if (!e.emit_tree(MRT_REF(MRT_REF_NODE, p.second), true)) return false;
-      s.blas_regions.push_back({b, e.n_slots(), 0, false});
-      it = blas.emplace(p.second, s.blas_regions.size() - 1).first;
-      e.push_end();
-    }
-    BlasRegion& r = s.blas_regions[it->second];
-    for (auto rs = std::lower_bound(s.rec_starts.begin(), s.rec_starts.end(), r.begin);
-         rs != s.rec_starts.end() && *rs < r.end; ++rs)
-      if (!rec_is_box(s.slots, *rs) && rec_kind(s.slots, *rs) != KIND_TRI)
+    BlasRegion* r = region_of(p.second);
+    if (!r) return false;
+    const uint32_t* w = s.slots.data();
+    for (auto rs = std::lower_bound(s.rec_starts.begin(), s.rec_starts.end(), r->begin);
+         rs != s.rec_starts.end() && *rs < r->end; ++rs)
+      if (!rec::is_box(w, *rs) && rec::kind(w, *rs) != KIND_TRI)
         return (err = "a volume target's BLAS must hold triangles only", false);
-    r.refs++;
-    if (s.slots[4 * (p.first + 1) + 2] == kVolModel) r.model = true;
-    s.slots[4 * p.first] = r.begin;
+    r->refs++;
+    if (rec::volume_target(w, p.first) == kVolModel) r->model = true;
+    rec::set_volume_blas(s.slots.data(), p.first, r->begin);
   }
   if (e.mix_alpha) s.trav_rng = true;
   if (sibling_layout) relayout(s);  // false: the plain preorder stream (tools/slab_check.cpp layout check)
@@ -666,11 +605,10 @@ bool build_host_scene(const mrt_scene_desc& d, HostScene& s, std::string& err, b
 
 namespace {
 
-double box_area(const std::vector<uint32_t>& w, uint32_t i) {
-  float v[6];
-  memcpy(v, &w[4 * i], 16);
-  memcpy(v + 4, &w[4 * (i + 1)], 8);
-  const double dx = (double)v[3] - v[0], dy = (double)v[4] - v[1], dz = (double)v[5] - v[2];
+double box_area(const uint32_t* w, uint32_t i) {
+  float mn[3], mx[3];
+  rec::box_bounds(w, i, mn, mx);
+  const double dx = (double)mx[0] - mn[0], dy = (double)mx[1] - mn[1], dz = (double)mx[2] - mn[2];
   const double a = 2.0 * (dx * dy + dy * dz + dz * dx);
   return a == a ? a : 1e300;  // NaN/inf boxes: treat as always visited
 }
@@ -678,8 +616,8 @@ double box_area(const std::vector<uint32_t>& w, uint32_t i) {
 }  // namespace
 
 void build_treelet(HostScene& s, uint32_t budget) {
-  const std::vector<uint32_t>& w = s.slots;
-  const uint32_t n = (uint32_t)(w.size() / 4);
+  const uint32_t* w = s.slots.data();
+  const uint32_t n = (uint32_t)(s.slots.size() / 4);
   s.tlet.clear();
   s.slots_tl.clear();
   s.tl_world_begin = s.world_begin;
@@ -691,7 +629,7 @@ void build_treelet(HostScene& s, uint32_t budget) {
     for (auto it = std::lower_bound(s.rec_starts.begin(), s.rec_starts.end(), b);
          it != s.rec_starts.end() && *it < e; ++it) {
       staged[*it] = 1;
-      used += rec_slots(w, *it);
+      used += rec::n_slots(w, *it);
     }
   };
   if (n <= budget) {
@@ -718,24 +656,21 @@ void build_treelet(HostScene& s, uint32_t budget) {
     //    the world roots and the roots of model BLAS (same space): a child's
     //    area never exceeds its parent's, so the chosen set is a rooted treelet
     std::priority_queue<std::pair<double, uint32_t>> pq;
-    std::vector<uint32_t> kids;
-    auto push_children = [&](uint32_t i) {
-      box_children(w, i, kids);
-      for (uint32_t j : kids)
-        if (rec_is_box(w, j) && !staged[j]) pq.push({box_area(w, j), j});
+    auto push_boxes = [&](uint32_t first, uint32_t end) {  // of a level
+      rec::for_each_in_level(w, first, end, [&](uint32_t j) {
+        if (rec::is_box(w, j) && !staged[j]) pq.push({box_area(w, j), j});
+      });
     };
-    for (uint32_t j = s.world_begin; j < n && w[4 * (j + 1) + 3] != KIND_END;
-         j = rec_is_box(w, j) ? w[4 * (j + 1) + 2] : rec_next(w, j))
-      if (rec_is_box(w, j)) pq.push({box_area(w, j), j});
+    push_boxes(s.world_begin, ~0u);
     for (size_t k = 0; k < s.blas_regions.size(); ++k)
-      if (!whole[k] && s.blas_regions[k].model && rec_is_box(w, s.blas_regions[k].begin))
+      if (!whole[k] && s.blas_regions[k].model && rec::is_box(w, s.blas_regions[k].begin))
         pq.push({box_area(w, s.blas_regions[k].begin), s.blas_regions[k].begin});
     while (!pq.empty() && used + 2 <= budget) {
       const uint32_t i = pq.top().second;
       pq.pop();
       staged[i] = 1;
       used += 2;
-      push_children(i);
+      push_boxes(rec::box_hit(w, i), rec::box_skip(w, i));
     }
   }
   // LDS image: the chosen records in stream order (whole regions stay together)
@@ -744,34 +679,30 @@ void build_treelet(HostScene& s, uint32_t budget) {
   for (uint32_t i : s.rec_starts)
     if (staged[i]) {
       lds_at[i] = at;
-      at += rec_slots(w, i);
-      if (rec_is_box(w, i)) s.tl_boxes++;
+      at += rec::n_slots(w, i);
+      if (rec::is_box(w, i)) s.tl_boxes++;
     }
   for (uint32_t i : s.rec_starts)  // an instance/model returns to the record after it: that one too
-    if (staged[i] && (rec_kind(w, i) == KIND_INST || rec_kind(w, i) == KIND_MODEL) &&
+    if (staged[i] && (rec::kind(w, i) == KIND_INST || rec::kind(w, i) == KIND_MODEL) &&
         !(i + 2 < n && staged[i + 2] && lds_at[i + 2] == lds_at[i] + 2))
       throw std::logic_error("treelet: a copied instance's successor is not copied after it");
   auto R = [&](uint32_t g) { return g < n && lds_at[g] != ~0u ? (kLdsTag | lds_at[g]) : g; };
-  auto rewrite = [&](uint32_t* rec) {  // rec: one record's slots (4 words each)
-    if (rec[7] & kBoxFlag) {
-      rec[6] = R(rec[6]);
-      rec[7] = kBoxFlag | R(rec[7] & ~kBoxFlag);
-    } else if (rec[7] == KIND_INST || rec[7] == KIND_MODEL) {
-      rec[1] = R(rec[1]);
-    } else if (rec[7] == KIND_TRI) {
-      rec[11] = R(rec[11]);
-    } else if (rec[7] == KIND_SPHERE || rec[7] == KIND_VOLUME) {
-      rec[5] = R(rec[5]);
-      if (rec[7] == KIND_VOLUME && rec[6]) rec[0] = R(rec[0]);  // its target's BLAS
-    }
+  // every index a record holds reaches the copy, but an instance's or model's
+  // BLAS end (the walk compares nothing with it: END records close regions)
+  auto rewrite = [&](uint32_t* r) {
+    rec::for_each_link(r, [&](uint32_t& index, rec::LinkKind k) {
+      if (k != rec::kLinkBlasEnd) index = R(index);
+    });
   };
-  s.slots_tl = w;
+  s.slots_tl = s.slots;
+  s.tlet.reserve(4 * (size_t)at);
   for (uint32_t i : s.rec_starts) {
-    rewrite(&s.slots_tl[4 * i]);
+    rewrite(rec::at(s.slots_tl.data(), i));
     if (staged[i]) {
-      const size_t at = s.tlet.size();
-      s.tlet.insert(s.tlet.end(), w.begin() + 4 * (size_t)i, w.begin() + 4 * (size_t)(i + rec_slots(w, i)));
-      rewrite(&s.tlet[at]);
+      const size_t t = s.tlet.size();
+      s.tlet.resize(t + 4 * (size_t)rec::n_slots(w, i));
+      rec::copy(&s.tlet[t], w, i);
+      rewrite(&s.tlet[t]);
     }
   }
   s.tl_world_begin = R(s.world_begin);

@@ -39,6 +39,38 @@ def test_sibling_layout_walks_like_the_preorder_stream(slab_check, scene):
     assert " 0 of 20000 rays differ" in r.stdout, r.stdout
 
 
+@pytest.mark.parametrize("scene", ["cornell", "sphere_grid", "cube_field"])
+def test_stream_mode_treelet_sizes(slab_check, scene):
+    """slab_check's `stream` mode (element counts and hashes of what the host builds, both layouts) and what
+    upload.h states for build_treelet: budget 0 gives no treelet; a budget the whole stream fits gives a treelet
+    of every record, its slot count the sum of the record sizes of rec_starts; slots_tl has the size of slots at
+    every other budget. That sum is the preorder stream's length up to the near-first trees (its nf_first_slot):
+    the preorder layout has no padding between records, and the sibling layout holds the same records.
+    No hash is compared: they are bound to one toolchain."""
+    r = subprocess.run([str(slab_check), scene, "0", str(GOLDEN), "stream"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    words, value = {}, {}  # (layout, item, budget) -> 32-bit elements; a scalar's value
+    for line in r.stdout.splitlines():
+        name, layout, item, budget, n, digest, val = line.split()
+        key = layout, item, None if budget == "-" else int(budget)
+        assert name == scene and len(digest) == 16 and key not in words, line
+        words[key] = int(n)
+        if val != "-":
+            value[key] = int(val)
+    record_slots = value["preorder", "nf_first_slot", None]
+    assert value["preorder", "nf_ok", None] == 1 and record_slots > 0
+    for layout in ("sibling", "preorder"):
+        n_words = words[layout, "slots", None]
+        assert n_words % 4 == 0 and n_words // 4 > record_slots  # the near-first trees follow the records
+        budgets = sorted(b for (lay, item, b) in words if lay == layout and item == "tlet")
+        assert budgets == sorted({0, 64, 1536, 4992, n_words // 4}), budgets
+        assert words[layout, "tlet", 0] == 0 and words[layout, "slots_tl", 0] == 0
+        for b in budgets[1:]:
+            assert words[layout, "slots_tl", b] == n_words, (layout, b)
+            assert 0 < words[layout, "tlet", b] <= 4 * b, (layout, b)
+        assert words[layout, "tlet", n_words // 4] == 4 * record_slots, layout
+
+
 @pytest.mark.slow
 def test_sibling_layout_mesh(slab_check, assets_dir):
     r = subprocess.run([str(slab_check), "mesh_ply", "20000", str(assets_dir), "layout"], capture_output=True, text=True,

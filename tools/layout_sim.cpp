@@ -29,27 +29,20 @@
 #include <vector>
 
 #include "../include/massrt.h"
+#include "device/records.h"
 #include "device/upload.h"
 
 using namespace mrt;
 
-static float f(uint32_t u) {
-  float x;
-  memcpy(&x, &u, 4);
-  return x;
-}
-
+// the record stream, read through records.h
 struct Stream {
-  const std::vector<uint32_t>& w;
-  uint32_t kind(uint32_t i) const { return w[4 * (i + 1) + 3]; }
-  bool box(uint32_t i) const { return (kind(i) & kBoxFlag) != 0; }
-  uint32_t size(uint32_t i) const { return box(i) ? 2 : (kind(i) == KIND_TRI ? 3 : 2); }
-  uint32_t hit(uint32_t i) const { return kind(i) & ~kBoxFlag; }
-  uint32_t skip(uint32_t i) const { return w[4 * (i + 1) + 2]; }
-  uint32_t next(uint32_t i) const {
-    const uint32_t k = kind(i);
-    return k == KIND_TRI ? w[4 * (i + 2) + 3] : (k == KIND_INST || k == KIND_MODEL) ? i + 2 : w[4 * (i + 1) + 1];
-  }
+  const uint32_t* w;
+  uint32_t kind(uint32_t i) const { return rec::kind(w, i); }
+  bool box(uint32_t i) const { return rec::is_box(w, i); }
+  uint32_t size(uint32_t i) const { return rec::n_slots(w, i); }
+  uint32_t hit(uint32_t i) const { return rec::box_hit(w, i); }
+  uint32_t skip(uint32_t i) const { return rec::box_skip(w, i); }
+  uint32_t next(uint32_t i) const { return rec::next(w, i); }
 };
 
 struct Ray {
@@ -65,9 +58,9 @@ static float trace(const Stream& s, uint32_t begin, const Ray& r, std::vector<ui
     if (seq) seq->push_back(i);
     const uint32_t k = s.kind(i);
     if (k == KIND_END) break;
-    const uint32_t* a = &s.w[4 * i];
     if (s.box(i)) {
-      float mn[3] = {f(a[0]), f(a[1]), f(a[2])}, mx[3] = {f(a[3]), f(a[4]), f(a[5])};
+      float mn[3], mx[3];
+      rec::box_bounds(s.w, i, mn, mx);
       float t0 = 0.001f, t1 = best;
       for (int c = 0; c < 3; ++c) {
         float inv = 1.0f / r.d[c];
@@ -80,7 +73,8 @@ static float trace(const Stream& s, uint32_t begin, const Ray& r, std::vector<ui
       continue;
     }
     if (k == KIND_TRI) {
-      float A[3] = {f(a[0]), f(a[1]), f(a[2])}, e1[3] = {f(a[3]), f(a[4]), f(a[5])}, e2[3] = {f(a[8]), f(a[9]), f(a[10])};
+      float A[3], e1[3], e2[3];
+      rec::tri_a(s.w, i, A), rec::tri_ab(s.w, i, e1), rec::tri_ac(s.w, i, e2);
       float p[3] = {r.d[1] * e2[2] - r.d[2] * e2[1], r.d[2] * e2[0] - r.d[0] * e2[2], r.d[0] * e2[1] - r.d[1] * e2[0]};
       float det = e1[0] * p[0] + e1[1] * p[1] + e1[2] * p[2];
       if (fabsf(det) > 1e-12f) {
@@ -137,15 +131,7 @@ static Tree parse(const Stream& s, uint32_t begin) {
   uint32_t i = begin;
   while (s.kind(i) != KIND_END) {
     t.recs.push_back(i);
-    if (s.box(i)) {
-      std::vector<uint32_t> k;
-      uint32_t c = s.hit(i), end = s.skip(i);
-      while (c < end) {
-        k.push_back(c);
-        c = s.box(c) ? s.skip(c) : s.next(c);
-      }
-      t.kids[i] = k;
-    }
+    if (s.box(i)) rec::box_children(s.w, i, t.kids[i]);
     i += s.size(i);
   }
   t.recs.push_back(i);  // END
@@ -239,8 +225,9 @@ static std::vector<uint32_t> sibling_bfs_top(const Stream& s, const Tree& t, uin
 // treelet), BFS order, then every other record in stream order
 static std::vector<uint32_t> hot_first(const Stream& s, const Tree& t, uint32_t root, size_t hot) {
   auto area = [&](uint32_t i) {
-    const uint32_t* a = &s.w[4 * i];
-    double dx = f(a[3]) - f(a[0]), dy = f(a[4]) - f(a[1]), dz = f(a[5]) - f(a[2]);
+    float mn[3], mx[3];
+    rec::box_bounds(s.w, i, mn, mx);
+    double dx = mx[0] - mn[0], dy = mx[1] - mn[1], dz = mx[2] - mn[2];
     return dx * dy + dy * dz + dz * dx;
   };
   std::vector<uint32_t> out;
@@ -294,7 +281,6 @@ int main(int argc, char** argv) {
   const char* scene = argc > 1 ? argv[1] : "mesh_ply";
   const char* assets = argc > 2 ? argv[2] : "assets";
   const int nrays = argc > 3 ? atoi(argv[3]) : 200000;
-  setenv("MRT_LAYOUT", "dfs", 1);  // the preorder stream: the layouts below are made from it
   mrt_builder* b = nullptr;
   mrt_builder_new(1, &b);
   if (mrt_builder_builtin(b, scene, 16.0f / 9.0f, assets) != MRT_OK) {
@@ -306,11 +292,11 @@ int main(int argc, char** argv) {
   mrt_builder_desc(b, &d, &cam);
   HostScene hs;
   std::string err;
-  if (!build_host_scene(d, hs, err)) {
+  if (!build_host_scene(d, hs, err, false)) {  // the preorder stream: the layouts below are made from it
     fprintf(stderr, "%s\n", err.c_str());
     return 1;
   }
-  Stream s{hs.slots};
+  Stream s{hs.slots.data()};
   // the region to study: the largest BLAS (mesh_ply: the 1M-triangle model), or the world
   uint32_t begin = hs.world_begin;
   size_t best_len = hs.world_end - hs.world_begin;

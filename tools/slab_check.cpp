@@ -20,6 +20,8 @@
 //   tools/slab_check mesh_ply 20000 assets [layout | nf | graze | tangent]
 //   tools/slab_check cornell 0 tests/golden hits|hits-nf rays.f32 out.u32
 //       n x 6 float32 rays in, n x 4 uint32 out in mrt_trace_rays' layout (k_rays_in -> walk -> k_rays_out)
+//   tools/slab_check eve 0 assets stream
+//       element counts and hashes of the stream, its tables and the treelet (stream_mode)
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -32,6 +34,7 @@
 #include <vector>
 
 #include "../mass-raytrace_amd/csrc/device/material.h"
+#include "../mass-raytrace_amd/csrc/device/records.h"
 #include "../mass-raytrace_amd/csrc/device/upload.h"
 #include "../mass-raytrace_amd/csrc/device/walk_nf.h"
 
@@ -72,11 +75,7 @@ struct BoundCheck {
 BoundCheck* g_bc = nullptr;
 // instance id -> its WILD entry's first slot (nf_bound.h NfWild; 0: not wild)
 std::unordered_map<uint32_t, uint32_t> g_wild_entry;
-NfWild wild_entry(const HostScene& s, uint32_t at) {
-  const uint32_t* e = s.slots.data() + 4 * (size_t)at;
-  auto fl = [&](int i) { float v; memcpy(&v, &e[i], 4); return v; };
-  return NfWild{{fl(0), fl(1), fl(2)}, {fl(3), fl(4), fl(5)}, fl(6), fl(7), fl(8), fl(9), {fl(10), fl(11), fl(12)}, fl(13)};
-}
+NfWild wild_entry(const HostScene& s, uint32_t at) { return rec::nf_wild_entry(s.slots.data(), at); }
 
 // NF tree parents (normal cones, round 6): every node a primitive's test
 // passes through on the near-first walk thickens its boxes by that node's
@@ -84,46 +83,29 @@ NfWild wild_entry(const HostScene& s, uint32_t at) {
 // holding the primitive's leaf, nf_parent the node above a node (~0: a root)
 std::unordered_map<uint32_t, uint32_t> g_nf_parent;
 std::vector<uint32_t> g_leaf_parent;
-uint32_t nf_vslot(const HostScene& s, const uint32_t* a) {
-  switch (a[7]) {
-    case KIND_TRI: return s.vnf_base[VNF_TRI] + (a[6] & kTriIdMask);
-    case KIND_SPHERE: return s.vnf_base[VNF_SPHERE] + a[4];
-    case KIND_INST: return s.vnf_base[VNF_INST] + a[0];
-    default: return s.vnf_base[VNF_MODEL] + a[0];
-  }
-}
 void map_nf_tree(const HostScene& s, uint32_t root, std::vector<uint8_t>& seen_blas) {
   const uint32_t* w = s.slots.data();
   std::vector<std::pair<uint32_t, uint32_t>> st{{root, ~0u}};
   while (!st.empty()) {
     const auto [i, par] = st.back();
     st.pop_back();
-    const uint32_t* a = w + 4 * (size_t)i;
-    if (a[7] & kBoxFlag) {
+    if (rec::is_box(w, i)) {
       g_nf_parent[i] = par;
-      const uint32_t base = a[7] & kNfIdx;
+      const uint32_t base = rec::nf_children(w, i);
       st.push_back({base, i});
-      st.push_back({base + 2 + ((a[3] >> 24) & 1u), i});
+      st.push_back({base + rec::nf_left_slots(w, i), i});
       continue;
     }
-    for (uint32_t r = i;;) {
-      const uint32_t* b = w + 4 * (size_t)r;
-      g_leaf_parent[nf_vslot(s, b)] = par;
-      uint32_t next;
-      if (b[7] == KIND_TRI) {
-        next = b[11];
-      } else if (b[7] == KIND_SPHERE) {
-        next = b[5];
-      } else {
-        if (b[7] == KIND_INST && b[3] != 0) g_wild_entry[b[0]] = b[3];
-        if (!seen_blas[b[1]]) {
-          seen_blas[b[1]] = 1;
-          map_nf_tree(s, b[1], seen_blas);
-        }
-        next = b[2];
+    for (uint32_t r = i; r != kNfPop; r = rec::nf_next(w, r)) {  // the leaf's records
+      g_leaf_parent[rec::vnf_slot(w, r, s.vnf_base)] = par;
+      const uint32_t k = rec::kind(w, r);
+      if (k != KIND_INST && k != KIND_MODEL) continue;
+      if (k == KIND_INST && rec::nf_wild(w, r) != 0) g_wild_entry[rec::object_id(w, r)] = rec::nf_wild(w, r);
+      const uint32_t blas = rec::nf_blas_root(w, r);
+      if (!seen_blas[blas]) {
+        seen_blas[blas] = 1;
+        map_nf_tree(s, blas, seen_blas);
       }
-      if (next == kNfPop) break;
-      r = next;
     }
   }
 }
@@ -138,8 +120,8 @@ float cone_rho_min(const HostScene& s, uint32_t vslot, V o, V d, float t, bool o
   if (!(B.kc > 0) || vslot >= g_leaf_parent.size()) return rho;
   const uint32_t* w = s.slots.data();
   for (uint32_t n = g_leaf_parent[vslot]; n != ~0u; n = g_nf_parent[n]) {
-    const uint32_t* a = w + 4 * (size_t)n;
-    rho = std::min(rho, nf_rho_cone(l, t, a[0], a[1], a[2], a[3], d));
+    const rec::NfFrame a = rec::nf_frame(w, n);
+    rho = std::min(rho, nf_rho_cone(l, t, a.ox, a.oy, a.oz, a.ew, d));
   }
   return rho;
 }
@@ -585,6 +567,62 @@ int run(int argc, char** argv, const mrt_scene_desc& d, const mrt_camera& cam, H
   return st.wrong ? 1 : 0;
 }
 
+// `stream` mode: what the host builds for the device, as element counts and
+// 64-bit FNV-1a hashes — the record stream and its tables under both layouts,
+// and the treelet at several budgets (slots). A change of the host code that
+// must leave the stream alone is checked by comparing these lines before and
+// after; the function reads HostScene's public fields only, so the same text
+// compiles against either side of such a change.
+int stream_mode(const char* scene, mrt_builder* b, const mrt_scene_desc& d) {
+  mrt_scene_ext ext{};
+  const mrt_volume_target* targets = nullptr;
+  uint32_t n_targets = 0;
+  mrt_builder_desc_ext(b, &ext);
+  mrt_builder_volume_targets(b, &targets, &n_targets);
+  // columns: scene, layout, item, treelet budget (-: none), elements, hash, the value of a scalar (-: an array)
+  auto line = [&](const char* layout, const char* item, long budget, const void* p, size_t n, size_t elem, bool scalar) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (size_t k = 0; k < n * elem; ++k) h = (h ^ static_cast<const uint8_t*>(p)[k]) * 0x100000001b3ull;
+    char bud[24] = "-", val[24] = "-";
+    if (budget >= 0) snprintf(bud, sizeof bud, "%ld", budget);
+    if (scalar) snprintf(val, sizeof val, "%u", *static_cast<const uint32_t*>(p));
+    printf("%-18s %-8s %-14s %8s %10zu %016llx %s\n", scene, layout, item, bud, n, (unsigned long long)h, val);
+  };
+  for (const bool sibling : {true, false}) {
+    const char* L = sibling ? "sibling" : "preorder";
+    HostScene s;
+    s.nf_build = kNfBuildAlways;
+    std::string err;
+    if (!build_host_scene(d, s, err, sibling, &ext, targets, n_targets)) return printf("%s: %s\n", scene, err.c_str()), 1;
+    auto vec = [&](const char* item, const std::vector<uint32_t>& v, long budget = -1) {
+      line(L, item, budget, v.data(), v.size(), 4, false);
+    };
+    auto one = [&](const char* item, uint32_t v, long budget = -1) { line(L, item, budget, &v, 1, 4, true); };
+    vec("slots", s.slots);
+    vec("rec_starts", s.rec_starts);
+    vec("vnf_leaf", s.vnf_leaf);
+    std::vector<uint32_t> regions;
+    for (const BlasRegion& r : s.blas_regions) regions.insert(regions.end(), {r.begin, r.end, r.refs, r.model ? 1u : 0u});
+    line(L, "blas_regions", -1, regions.data(), s.blas_regions.size(), 16, false);
+    one("world_begin", s.world_begin);
+    one("world_end", s.world_end);
+    one("nf_ok", s.nf_ok ? 1u : 0u);
+    one("nf_world", s.nf_world);
+    one("nf_wild_root", s.nf_wild_root);
+    one("nf_first_slot", s.nf_first_slot);
+    line(L, "vnf_base", -1, s.vnf_base, 4, 4, false);
+    const long whole = (long)(s.slots.size() / 4);  // a budget the whole stream fits
+    for (const long budget : {0l, 64l, 1536l, 4992l, whole}) {
+      build_treelet(s, (uint32_t)budget);
+      vec("tlet", s.tlet, budget);
+      vec("slots_tl", s.slots_tl, budget);
+      one("tl_world_begin", s.tl_world_begin, budget);
+      one("tl_boxes", s.tl_boxes, budget);
+    }
+  }
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -599,6 +637,11 @@ int main(int argc, char** argv) {
   mrt_scene_desc d;
   mrt_camera cam;
   mrt_builder_desc(b, &d, &cam);
+  if (argc > 4 && !strcmp(argv[4], "stream")) {  // every scene, those whose traversal draws random numbers too
+    const int rc = stream_mode(argv[1], b, d);
+    mrt_builder_free(b);
+    return rc;
+  }
   HostScene s;
   s.keep_nf_boxes = true;  // the bound checks' leaf boxes
   s.nf_build = kNfBuildAlways;  // the trees even where the per-scene rule would walk the reference's way
