@@ -47,9 +47,7 @@ void set_option(mrt_ctx* c, int id, int64_t v) {
   if (!why.empty()) throw ApiError{MRT_ERR_INVALID, why};
   if (id == OPT_QUEUES && v != c->opt[id] && c->pool_mem) {  // the pool is split per queue: reallocated at the next render
     HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipFree(c->pool_mem));
-    c->pool_mem = nullptr;
-    c->pool_cap = 0;
+    release_pool(c);
     c->grids.clear();  // k_trace's grid share depends on the queue count
   }
   c->opt[id] = v;

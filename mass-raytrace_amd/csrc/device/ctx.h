@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../../include/massrt.h"
+#include "../host/loop.h"
 #include "../host/options.h"
 #include "frames.h"
 #include "pool.h"
@@ -197,6 +198,7 @@ uint32_t persistent_grid(mrt_ctx* c, const void* f, size_t smem, bool shared = f
 
 // ---- render.hip ----
 void wait_queues(mrt_ctx* c, hipStream_t st);
+void release_pool(mrt_ctx* c);  // frees the path pool; the caller has synchronised the device
 void ensure_pool(mrt_ctx* c, size_t P);
 void ensure_slots(mrt_ctx* c, size_t n);
 std::vector<uint32_t> shard_pixel_list(uint32_t W, uint32_t H, uint32_t si, uint32_t sc);

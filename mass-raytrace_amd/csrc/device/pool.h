@@ -32,6 +32,10 @@ struct Ctrl {
   // XCD group: group g takes its rays from the g-th eighth of the pool
   uint32_t group_next[kGroups * 32];
 };
+// The Ctrl a launch sequence starts from (copied to the device): pool 0 holds
+// `active0` paths, everything else zero but next_work, k_render's work counter
+// (mrt_trace_rays starts it at its ray count: none is left to hand out).
+inline Ctrl ctrl_init(uint32_t active0, uint32_t next_work = 0) { return Ctrl{{active0, 0}, next_work, 0}; }
 
 // SoA path state, 5 x 16 B per slot:
 //   ro  = {o.x, o.y, o.z, work index g}    rd  = {d.x, d.y, d.z, bounces k}
@@ -61,11 +65,6 @@ struct RenderParams {
   uint32_t pool_cap;     // path slots per buffer
   const uint32_t* pixlist;
   uint32_t shade_bin;    // k_shade: survivors grouped by material kind and direction in the next pool (option shade_bin)
-};
-
-// Lagged status read of a queue (k_status): the fields the host loop needs.
-struct HostStatus {
-  uint32_t active0, active1, shade_short, work;
 };
 
 constexpr float kTmin = 0.001f;          // World::intersect(ray, 0.001, INFINITY) (main.rs trace)

@@ -46,18 +46,24 @@ __device__ __forceinline__ void gen_work(const DevCamera& cam, const RenderParam
   rs = rng_pack(rng);
 }
 
+// The new camera path of work item g into slot i of a pool.
+__device__ __forceinline__ void gen_path(const DevCamera& cam, const RenderParams& rp, const PathBufs& out, uint32_t g,
+                                         uint32_t i) {
+  float4 ro, rd;
+  uint4 rs;
+  gen_work(cam, rp, g, ro, rd, rs);
+  out.ro[i] = ro;
+  out.rd[i] = rd;
+  out.thr[i] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);  // L = 0: rad not written
+  out.rng[i] = rs;
+}
+
 // Initial pool: work items [base, base + n0) into slots [0, n0).
 __global__ __launch_bounds__(kBlock) void k_generate(DevCamera cam, RenderParams rp, PathBufs out, uint32_t base,
                                                      uint32_t n0) {
   uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n0) return;
-  float4 ro, rd;
-  uint4 rs;
-  gen_work(cam, rp, base + i, ro, rd, rs);
-  out.ro[i] = ro;
-  out.rd[i] = rd;
-  out.thr[i] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);  // L = 0: rad not written
-  out.rng[i] = rs;
+  gen_path(cam, rp, out, base + i, i);
 }
 
 // Lagged status read of a queue (host loop, one per batch): the fields the
@@ -81,27 +87,22 @@ __global__ void k_status(const Ctrl* ctrl, const uint32_t* work, HostStatus* out
 // pool (ctrl->active[cur ^ 1] of them): reserve work items for the free slots
 // behind them from the shared work counter. One thread; the counter is only
 // advanced while it is below G, so it passes G by at most a pool per queue.
+// What to generate and what to move is loop.h's plan_refill.
 __global__ void k_reserve(Ctrl* ctrl, uint32_t cur, uint32_t* work, uint32_t G, uint32_t cap) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   const unsigned long long sv = ctrl->surv[cur ^ 1];  // 0 unless shade_bin 2
-  const uint32_t lo = ctrl->active[cur ^ 1] + (uint32_t)sv, hi = (uint32_t)(sv >> 32), n = lo + hi;
-  const uint32_t want = n < cap ? cap - n : 0u;
-  uint32_t m = 0, base = G;
-  if (want && __hip_atomic_load(work, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < G) {
-    base = atomicAdd(work, want);
-    m = base < G ? (G - base < want ? G - base : want) : 0u;
-  }
-  ctrl->gen_slot = lo;
-  ctrl->gen_count = m;
-  ctrl->gen_base = base;
-  // the top block [cap - hi, cap) closes onto the refill's end lo + m: its
-  // paths at or past the new end E move into the free slots below E
-  const uint32_t E = n + m, g = cap - E;
-  const uint32_t mv = g < hi ? g : hi;
-  ctrl->gen_move = mv;
-  ctrl->gen_move_src = cap - mv;
-  ctrl->gen_move_dst = lo + m;
-  ctrl->active[cur ^ 1] = E;
+  const uint32_t lo = ctrl->active[cur ^ 1] + (uint32_t)sv, hi = (uint32_t)(sv >> 32);
+  const uint32_t want = refill_want(lo + hi, cap);
+  uint32_t base = G;
+  if (want && __hip_atomic_load(work, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < G) base = atomicAdd(work, want);
+  const RefillPlan p = plan_refill(lo, hi, cap, G, base);
+  ctrl->gen_slot = p.gen_slot;
+  ctrl->gen_count = p.gen_count;
+  ctrl->gen_base = p.gen_base;
+  ctrl->gen_move = p.gen_move;
+  ctrl->gen_move_src = p.gen_move_src;
+  ctrl->gen_move_dst = p.gen_move_dst;
+  ctrl->active[cur ^ 1] = p.active;
   ctrl->surv[cur ^ 1] = 0;
 }
 
@@ -122,16 +123,8 @@ __global__ __launch_bounds__(kBlock) void k_refill(DevCamera cam, RenderParams r
     out.rng[b] = rs;
     if (holds_l(thr)) out.rad[b] = out.rad[a];
   }
-  for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < m; j += gridDim.x * kBlock) {
-    float4 ro, rd;
-    uint4 rs;
-    gen_work(cam, rp, base + j, ro, rd, rs);
-    const uint32_t i = slot + j;
-    out.ro[i] = ro;
-    out.rd[i] = rd;
-    out.thr[i] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);  // L = 0: rad not written
-    out.rng[i] = rs;
-  }
+  for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < m; j += gridDim.x * kBlock)
+    gen_path(cam, rp, out, base + j, slot + j);
 }
 
 // k_shade only shades and compacts: new camera rays go in behind the
@@ -150,7 +143,7 @@ __global__ __launch_bounds__(kShadeBlock, WPE) void k_shade(DevScene S, RenderPa
   const uint32_t n = ctrl->active[cur];
   if (blockIdx.x == 0 && threadIdx.x < kGroups) ctrl->group_next[threadIdx.x * 32] = 0;  // next k_trace
   // one workgroup per 256 live paths: the host sizes the grid from a bound on
-  // the live count (shade_grid), so a drain launch does not dispatch a
+  // the live count (shade_workgroups), so a drain launch does not dispatch a
   // workgroup per 256 slots of the whole pool. A bound that fell short is
   // reported to the host, never dropped silently. (A grid-stride loop here
   // made the kernel spill 80 B instead of 44 and cost 3.5% of the frame.)
@@ -403,44 +396,22 @@ RenderFn render_kernel(bool count, bool alpha, bool adopt) {
   });
 }
 
-// k_shade's grid for a pool known to hold at most `bound` live paths: one
-// workgroup per 256 of them.
-// While the work counter has items left the pool refills to capacity; once
-// it is exhausted the live count only falls, so the last status the host
-// read bounds every later launch — a drain launch then dispatches a few
-// workgroups instead of one per 256 slots of the whole pool.
-uint32_t shade_grid(const Queue& q, size_t bound) {
-  const size_t n = std::min(q.cap, bound);
-  return (uint32_t)std::max<size_t>(1, (n + kShadeBlock - 1) / kShadeBlock);
-}
-
-// device bytes of a pool of P paths over the context's queues: two state
-// sets (5 x 16 B each) + the hit record per path, 256-B aligned sections
-constexpr size_t kPathBytes = 16 * (2 * 5 + 1);
-size_t pool_bytes(const mrt_ctx* c, size_t P) {
-  const size_t K = (size_t)c->tun.queues, per_q = (P + K - 1) / K;
-  return (kPathBytes * per_q + 4096) * K;
-}
-
 // Sizes a render's path pool and results slab to the device:
 // they must fit the memory free now minus mem_reserve, since several
 // contexts may share one device (a multi-device context over {0,0,0}, ranks
 // rehearsed on one GPU) and the defaults alone ask for ~98 GiB. When either
-// buffer has to grow both are released and planned afresh: the pool shrinks
-// first (its size barely matters from 128M paths on), down to
-// kPoolFloor paths, then the samples per results chunk (more chunks, the
-// same image: chunks accumulate in sample order). The planning of the
-// contexts of a process is serialised, so each sees the others' buffers.
-constexpr size_t kPoolFloor = (size_t)64 << 20;
+// buffer has to grow both are released and planned afresh (loop.h's
+// plan_sizes: the pool shrinks first, then the samples per results chunk).
+// The planning of the contexts of a process is serialised, so each sees the
+// others' buffers.
 std::mutex g_alloc_mutex;
 void plan_buffers(mrt_ctx* c, uint32_t n_pix, uint32_t& spp_chunk, bool need_pool) {
   std::lock_guard<std::mutex> lock(g_alloc_mutex);
-  size_t P = need_pool ? std::min<size_t>((size_t)n_pix * spp_chunk, c->tun.pool_paths) : 0;
-  if (P <= c->pool_cap && (size_t)n_pix * spp_chunk <= c->results_cap) return;
+  if (pool_wanted(n_pix, spp_chunk, c->tun.pool_paths, need_pool) <= c->pool_cap &&
+      (size_t)n_pix * spp_chunk <= c->results_cap)
+    return;
   HIP_CHECK(hipDeviceSynchronize());  // the queues may still use the old buffers
-  if (c->pool_mem) HIP_CHECK(hipFree(c->pool_mem));
-  c->pool_mem = nullptr;
-  c->pool_cap = 0;
+  release_pool(c);
   if (c->results) HIP_CHECK(hipFree(c->results));
   c->results = nullptr;
   c->results_cap = 0;
@@ -448,20 +419,12 @@ void plan_buffers(mrt_ctx* c, uint32_t n_pix, uint32_t& spp_chunk, bool need_poo
   HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
   const size_t reserve = c->tun.mem_reserve;
   const size_t budget = free_b > reserve ? free_b - reserve : 0;
-  for (;;) {
-    const size_t need = (P ? pool_bytes(c, P) : 0) + (size_t)n_pix * spp_chunk * 16;
-    if (need <= budget) break;
-    if (P > kPoolFloor) {
-      P = std::max(kPoolFloor, P / 2);
-    } else if (spp_chunk > 1) {
-      spp_chunk = spp_chunk / 2;
-      if (P) P = std::min<size_t>(P, (size_t)n_pix * spp_chunk);
-    } else {
-      throw ApiError{MRT_ERR_NOMEM, "device memory: " + std::to_string(free_b >> 20) + " MiB free, mem_reserve_mb " +
-                                        std::to_string(reserve >> 20) + ": not even one sample per pixel fits"};
-    }
-  }
-  if (P) ensure_pool(c, P);
+  const SizePlan plan = plan_sizes(n_pix, spp_chunk, c->tun.pool_paths, c->tun.queues, budget, need_pool);
+  if (!plan.fits)
+    throw ApiError{MRT_ERR_NOMEM, "device memory: " + std::to_string(free_b >> 20) + " MiB free, mem_reserve_mb " +
+                                      std::to_string(reserve >> 20) + ": not even one sample per pixel fits"};
+  spp_chunk = plan.spp_chunk;
+  if (plan.P) ensure_pool(c, plan.P);
   HIP_CHECK(hipMalloc(&c->results, (size_t)n_pix * spp_chunk * 16));  // released above
   c->results_cap = (size_t)n_pix * spp_chunk;
 }
@@ -495,6 +458,14 @@ void launch_finish(mrt_ctx* c, int qi, uint32_t cur, const RenderParams& rp, boo
   HIP_CHECK(hipGetLastError());
 }
 
+// Folds a chunk's results slab into the caller's accumulation buffers on `st`
+// (k_accumulate: in sample order).
+void accumulate(mrt_ctx* c, const RenderParams& rp, float* d_rgb, uint32_t* d_b, hipStream_t st) {
+  hipLaunchKernelGGL(k_accumulate, dim3((rp.n_pix + kAccPix - 1) / kAccPix), dim3(kBlock), 0, st,
+                     (const float4*)c->results, rp.n_pix, rp.spp, rp.pixlist, d_rgb, d_b);
+  HIP_CHECK(hipGetLastError());
+}
+
 // The fused path loop: one k_render launch + one k_accumulate per chunk.
 void render_fused(mrt_ctx* c, const mrt_render_args* a, const uint32_t* pixlist_d, uint32_t n_pix, uint32_t spp_chunk,
                   float* d_rgb, uint32_t* d_b, hipStream_t st) {
@@ -506,7 +477,7 @@ void render_fused(mrt_ctx* c, const mrt_render_args* a, const uint32_t* pixlist_
     const uint32_t cs = std::min(spp_chunk, a->spp_count - done);
     if (a->max_depth == 0) continue;  // trace(ray, 0) returns (0, 0): nothing to add
     const RenderParams rp = chunk_params(c, a, pixlist_d, n_pix, done, cs, 0);
-    Ctrl init{{0, 0}, 0, 0};
+    const Ctrl init = ctrl_init(0);
     HIP_CHECK(hipMemcpyAsync(c->q[0].ctrl, &init, sizeof(Ctrl), hipMemcpyHostToDevice, st));
     if (timing) HIP_CHECK(hipEventRecord(c->tev[0], st));
     const RenderFn f = render_kernel(count, c->scene_alpha, false);
@@ -524,9 +495,7 @@ void render_fused(mrt_ctx* c, const mrt_render_args* a, const uint32_t* pixlist_
       c->kstats.trace_launches++;
       c->kstats.iterations++;
     }
-    hipLaunchKernelGGL(k_accumulate, dim3((n_pix + kAccPix - 1) / kAccPix), dim3(kBlock), 0, st, (const float4*)c->results,
-                       n_pix, cs, pixlist_d, d_rgb, d_b);
-    HIP_CHECK(hipGetLastError());
+    accumulate(c, rp, d_rgb, d_b, st);
   }
   mark_ctx_busy(c, st);
 }
@@ -543,16 +512,20 @@ void wait_queues(mrt_ctx* c, hipStream_t st) {
     if (q.join) HIP_CHECK(hipStreamWaitEvent(st, q.join, 0));
 }
 
+void release_pool(mrt_ctx* c) {
+  if (c->pool_mem) HIP_CHECK(hipFree(c->pool_mem));
+  c->pool_mem = nullptr;
+  c->pool_cap = 0;
+}
+
 // P paths over the context's queues.
 void ensure_pool(mrt_ctx* c, size_t P) {
   if (P <= c->pool_cap) return;
   HIP_CHECK(hipDeviceSynchronize());  // the queues may still be draining into the old pool
-  if (c->pool_mem) HIP_CHECK(hipFree(c->pool_mem));
-  c->pool_mem = nullptr;
-  c->pool_cap = 0;
+  release_pool(c);
   const int K = c->tun.queues;
   const size_t per_q = (P + K - 1) / K;
-  HIP_CHECK(hipMalloc(&c->pool_mem, pool_bytes(c, P)));
+  HIP_CHECK(hipMalloc(&c->pool_mem, pool_bytes(K, P)));
   char* p = (char*)c->pool_mem;
   auto take = [&](size_t bytes) {
     char* r = p;
@@ -622,187 +595,213 @@ std::pair<uint32_t*, uint32_t> pixlist(mrt_ctx* c, uint32_t W, uint32_t H, uint3
 // orders that render after this work too.
 void mark_ctx_busy(mrt_ctx* c, hipStream_t st) { HIP_CHECK(hipEventRecord(c->acc_done, st)); }
 
-void render_device(mrt_ctx* c, const mrt_render_args* a, float* d_rgb, uint32_t* d_b, hipStream_t st) {
-  if (!a) throw ApiError{MRT_ERR_INVALID, "null render args"};
-  if (!c->has_scene) throw ApiError{MRT_ERR_STATE, "no scene uploaded"};
-  if (!c->has_camera) throw ApiError{MRT_ERR_STATE, "no camera set"};
-  if (a->width == 0 || a->height == 0) throw ApiError{MRT_ERR_INVALID, "empty image"};
-  if ((uint64_t)a->width * a->height >= (1ull << 32)) throw ApiError{MRT_ERR_INVALID, "image too large"};
-  uint32_t sc = a->shard_count ? a->shard_count : 1;
-  if (a->shard_index >= sc) throw ApiError{MRT_ERR_INVALID, "shard_index >= shard_count"};
-  if (a->spp_count == 0) return;
-  if ((uint64_t)a->spp_begin + a->spp_count > 0xFFFFFFFFull) throw ApiError{MRT_ERR_INVALID, "sample index overflow"};
-  auto pl = pixlist(c, a->width, a->height, a->shard_index, sc);
-  const uint32_t n_pix = pl.second;
-  if (n_pix == 0) return;
-  const bool count = (a->flags & MRT_RENDER_COUNTERS) != 0;
-  const bool simple = (a->flags & MRT_RENDER_SIMPLE_TRACE) != 0;
-  const bool scene_rng = c->facts.trav_rng;
-  // results slab <= results_max samples (16 B each); pool <= pool_paths
-  uint32_t spp_chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(a->spp_count, c->tun.results_max / n_pix));
-  if (simple && c->scene_ext)
-    throw ApiError{MRT_ERR_INVALID, "MRT_RENDER_SIMPLE_TRACE does not support composite surfaces, CubeMap backgrounds or Eve materials"};
-  if ((a->flags & MRT_RENDER_FUSED) && !simple) {
-    if (scene_rng)
-      throw ApiError{MRT_ERR_INVALID, "MRT_RENDER_FUSED does not support scenes whose traversal draws (Volume, Mix alpha)"};
-    if (c->scene_ext)
-      throw ApiError{MRT_ERR_INVALID, "MRT_RENDER_FUSED does not support composite surfaces, CubeMap backgrounds or Eve materials"};
-    render_fused(c, a, pl.first, n_pix, spp_chunk, d_rgb, d_b, st);
-    return;
-  }
-  plan_buffers(c, n_pix, spp_chunk, true);
-  const int K = c->tun.queues;
-  const bool timing = (a->flags & MRT_RENDER_TIME_KERNELS) != 0;
-  if (timing && c->pend_marks.size() + c->pend_fin.size() > kMaxPendingMarks) resolve_kernel_timing(c);
-  // the drain hand-off (launch_finish): the fused kernel has no traversal
-  // draws or composite surfaces; its lane-ray slots are allocated here, before
-  // any queue runs (ensure_slots reallocates)
-  const bool can_finish = !scene_rng && !c->scene_ext && !simple;
-  const uint32_t finish_paths = can_finish ? c->tun.finish_paths : 0u;
-  if (finish_paths) ensure_slots(c, (size_t)finish_grid(c, count) * kBlock * kMaxQueues);
-  auto next_event = [&]() {
+namespace {
+
+// The kernel-timing marks of a render: stamp(stream) records an event of the
+// context's pool on the stream and returns it when the render is timed, null
+// otherwise. A chunk's marks wait here until its queues are joined (keep),
+// then in the context until the stats are read (resolve_kernel_timing).
+struct Stamps {
+  mrt_ctx* c;
+  bool timing;
+  std::vector<std::array<hipEvent_t, 3>> marks;  // an iteration: before k_trace, before k_shade, after the refill
+  std::vector<std::array<hipEvent_t, 2>> fin;    // around a hand-off launch
+  hipEvent_t stamp(hipStream_t s) {
+    if (!timing) return nullptr;
     if (c->ev_used == c->ev_pool.size()) {
       hipEvent_t e;
       HIP_CHECK(hipEventCreate(&e));
       c->ev_pool.push_back(e);
     }
-    return c->ev_pool[c->ev_used++];
-  };
+    hipEvent_t e = c->ev_pool[c->ev_used++];
+    HIP_CHECK(hipEventRecord(e, s));
+    return e;
+  }
+  void keep() {  // resolved by mrt_get_kernel_stats (resolve_kernel_timing)
+    c->pend_marks.insert(c->pend_marks.end(), marks.begin(), marks.end());
+    c->pend_fin.insert(c->pend_fin.end(), fin.begin(), fin.end());
+    marks.clear();
+    fin.clear();
+  }
+};
+
+// What the chunks of one wavefront render share.
+struct Pass {
+  bool count, simple;
+  uint32_t finish_paths;  // drain hand-off threshold (0: never)
+  ShadeFn shade;
+};
+
+// The argument and state errors of a render, before anything is enqueued.
+void check_render_args(const mrt_ctx* c, const mrt_render_args* a) {
+  if (!a) throw ApiError{MRT_ERR_INVALID, "null render args"};
+  if (!c->has_scene) throw ApiError{MRT_ERR_STATE, "no scene uploaded"};
+  if (!c->has_camera) throw ApiError{MRT_ERR_STATE, "no camera set"};
+  if (a->width == 0 || a->height == 0) throw ApiError{MRT_ERR_INVALID, "empty image"};
+  if ((uint64_t)a->width * a->height >= (1ull << 32)) throw ApiError{MRT_ERR_INVALID, "image too large"};
+  if (a->shard_index >= (a->shard_count ? a->shard_count : 1))
+    throw ApiError{MRT_ERR_INVALID, "shard_index >= shard_count"};
+  if ((uint64_t)a->spp_begin + a->spp_count > 0xFFFFFFFFull) throw ApiError{MRT_ERR_INVALID, "sample index overflow"};
+}
+
+// What the scene rules out for the render's flags.
+void check_render_flags(const mrt_ctx* c, const mrt_render_args* a) {
+  const bool simple = (a->flags & MRT_RENDER_SIMPLE_TRACE) != 0;
+  if (simple && c->scene_ext)
+    throw ApiError{MRT_ERR_INVALID, "MRT_RENDER_SIMPLE_TRACE does not support composite surfaces, CubeMap backgrounds or Eve materials"};
+  if ((a->flags & MRT_RENDER_FUSED) && !simple) {
+    if (c->facts.trav_rng)
+      throw ApiError{MRT_ERR_INVALID, "MRT_RENDER_FUSED does not support scenes whose traversal draws (Volume, Mix alpha)"};
+    if (c->scene_ext)
+      throw ApiError{MRT_ERR_INVALID, "MRT_RENDER_FUSED does not support composite surfaces, CubeMap backgrounds or Eve materials"};
+  }
+}
+
+// fork: the queues start after the accumulate that last read the slab
+// (acc_done, on the caller's stream; the kernels read nothing else the
+// caller's stream writes). The shared work counter starts behind the chunk's
+// first n0 paths, which k_generate deals over the queues' pools.
+void fork_queues(mrt_ctx* c, const RenderParams& rp) {
+  const int K = c->tun.queues;
+  const uint32_t n0 = (uint32_t)std::min<size_t>(rp.G, c->pool_cap);
+  HIP_CHECK(hipStreamWaitEvent(c->q[0].stream, c->acc_done, 0));
+  HIP_CHECK(hipMemcpyAsync(c->work, &n0, 4, hipMemcpyHostToDevice, c->q[0].stream));
+  HIP_CHECK(hipEventRecord(c->set_fork, c->q[0].stream));
+  uint32_t base = 0;
+  for (int k = 0; k < K; ++k) {
+    Queue& q = c->q[k];
+    const uint32_t nk = queue_share(n0, K, k);  // <= q.cap
+    if (k) HIP_CHECK(hipStreamWaitEvent(q.stream, c->set_fork, 0));
+    const Ctrl init = ctrl_init(nk);
+    HIP_CHECK(hipMemcpyAsync(q.ctrl, &init, sizeof(Ctrl), hipMemcpyHostToDevice, q.stream));
+    if (nk) {
+      hipLaunchKernelGGL(k_generate, dim3((nk + kBlock - 1) / kBlock), dim3(kBlock), 0, q.stream, c->cam, rp,
+                         q.bufs[0], base, nk);
+      HIP_CHECK(hipGetLastError());
+    }
+    base += nk;
+  }
+}
+
+// kBatch iterations of queue q — k_trace, k_shade and the refill — and the
+// status read behind them (k_status into slot L.slot, then the slot's event).
+void enqueue_batch(mrt_ctx* c, Queue& q, QueueLoop& L, const RenderParams& rp, const Pass& p, Stamps& t) {
+  for (int b = 0; b < kBatch; ++b, ++L.it) {
+    const uint32_t cur = L.it & 1;
+    const hipEvent_t m0 = t.stamp(q.stream);
+    if (p.simple)
+      launch_trace_simple(c, q, cur);
+    else
+      launch_trace(c, q.stream, q, q.bufs[cur], cur, p.count, kTmin, INFINITY);
+    const hipEvent_t m1 = t.stamp(q.stream);
+    hipLaunchKernelGGL(p.shade, dim3(shade_workgroups(q.cap, L.bound, kShadeBlock)), dim3(kShadeBlock), 0, q.stream,
+                       c->S, rp, q.bufs[cur], q.bufs[cur ^ 1], (const uint4*)q.hits, q.ctrl, cur, c->results, c->d_cnt);
+    HIP_CHECK(hipGetLastError());
+    if (!L.exhausted || rp.shade_bin == 2) {  // new paths behind the survivors (shade_bin 2: and the pool's ends joined)
+      hipLaunchKernelGGL(k_reserve, dim3(1), dim3(64), 0, q.stream, q.ctrl, cur, c->work, rp.G, rp.pool_cap);
+      hipLaunchKernelGGL(k_refill, dim3(c->refill_grid), dim3(kBlock), 0, q.stream, c->cam, rp, q.bufs[cur ^ 1],
+                         (const Ctrl*)q.ctrl);
+      HIP_CHECK(hipGetLastError());
+    }
+    const hipEvent_t m2 = t.stamp(q.stream);
+    if (t.timing) t.marks.push_back({m0, m1, m2});
+  }
+  hipLaunchKernelGGL(k_status, dim3(1), dim3(64), 0, q.stream, (const Ctrl*)q.ctrl, (const uint32_t*)c->work,
+                     q.d_stat + L.slot);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(q.ev[L.slot], q.stream));
+}
+
+// an internal error in the middle of a chunk: every queue's kernels end
+// before the error returns, so the next render does not fork onto pools
+// and a results slab that this chunk's launches still write
+[[noreturn]] void fail_chunk(mrt_ctx* c, const std::string& msg) {
+  for (int k = 0; k < c->tun.queues; ++k) (void)hipStreamSynchronize(c->q[k].stream);
+  throw ApiError{MRT_ERR_HIP, msg};
+}
+
+// Waits for the status of the batch before the one just queued (one batch
+// stays in flight) and acts on what on_status makes of it; true: queue k
+// finished.
+bool read_status(mrt_ctx* c, int k, QueueLoop& L, const RenderParams& rp, const Pass& p, Stamps& t) {
+  Queue& q = c->q[k];
+  HIP_CHECK(hipEventSynchronize(q.ev[L.slot ^ 1]));
+  const volatile HostStatus& v = q.h_stat[L.slot ^ 1];  // written by the GPU
+  const HostStatus s{v.active0, v.active1, v.shade_short, v.work};
+  const LoopStep step = on_status(L, s, rp.G, p.finish_paths);
+  if (step == LoopStep::kShadeShort)
+    fail_chunk(c, "internal: a k_shade grid was smaller than its live pool (" + std::to_string(s.shade_short) + " paths)");
+  if (step == LoopStep::kHandOff) {
+    const hipEvent_t f0 = t.stamp(q.stream);
+    launch_finish(c, k, L.it & 1, rp, p.count, c->results);
+    const hipEvent_t f1 = t.stamp(q.stream);
+    if (t.timing) t.fin.push_back({f0, f1});
+  }
+  return step != LoopStep::kGoOn;
+}
+
+// The host loop of a chunk: every open queue in turn enqueues a batch and
+// reads the status of its batch before, until each has finished.
+void run_queues(mrt_ctx* c, const RenderParams& rp, const Pass& p, Stamps& t) {
+  const int K = c->tun.queues;
+  QueueLoop loop[kMaxQueues];
+  int open = K;
+  while (open > 0) {
+    for (int k = 0; k < K; ++k) {
+      QueueLoop& L = loop[k];
+      if (L.finished) continue;
+      enqueue_batch(c, c->q[k], L, rp, p, t);
+      if (L.pending && read_status(c, k, L, rp, p, t)) --open;
+      L.pending = true;
+      L.slot ^= 1;
+      if (L.it > kMaxIterations) fail_chunk(c, "render did not converge");
+    }
+  }
+}
+
+// join: `st` continues after every queue (which may still be running its
+// drain: the host does not wait)
+void join_queues(mrt_ctx* c, hipStream_t st) {
+  for (int k = 0; k < c->tun.queues; ++k) {
+    HIP_CHECK(hipEventRecord(c->q[k].join, c->q[k].stream));
+    HIP_CHECK(hipStreamWaitEvent(st, c->q[k].join, 0));
+  }
+}
+
+}  // namespace
+
+void render_device(mrt_ctx* c, const mrt_render_args* a, float* d_rgb, uint32_t* d_b, hipStream_t st) {
+  check_render_args(c, a);
+  if (a->spp_count == 0) return;
+  auto pl = pixlist(c, a->width, a->height, a->shard_index, a->shard_count ? a->shard_count : 1);
+  const uint32_t n_pix = pl.second;
+  if (n_pix == 0) return;
+  check_render_flags(c, a);
+  const bool count = (a->flags & MRT_RENDER_COUNTERS) != 0;
+  const bool simple = (a->flags & MRT_RENDER_SIMPLE_TRACE) != 0;
+  uint32_t spp_chunk = first_chunk(a->spp_count, c->tun.results_max, n_pix);
+  if ((a->flags & MRT_RENDER_FUSED) && !simple) {
+    render_fused(c, a, pl.first, n_pix, spp_chunk, d_rgb, d_b, st);
+    return;
+  }
+  plan_buffers(c, n_pix, spp_chunk, true);
+  Stamps stamps{c, (a->flags & MRT_RENDER_TIME_KERNELS) != 0};
+  if (stamps.timing && c->pend_marks.size() + c->pend_fin.size() > kMaxPendingMarks) resolve_kernel_timing(c);
+  // the drain hand-off (launch_finish): the fused kernel has no traversal
+  // draws or composite surfaces; its lane-ray slots are allocated here, before
+  // any queue runs (ensure_slots reallocates)
+  const bool can_finish = !c->facts.trav_rng && !c->scene_ext && !simple;
+  const Pass p{count, simple, can_finish ? c->tun.finish_paths : 0u, shade_kernel(count, c->scene_ext, c->tun.shade_wpe)};
+  if (p.finish_paths) ensure_slots(c, (size_t)finish_grid(c, count) * kBlock * kMaxQueues);
   for (uint32_t done = 0; done < a->spp_count; done += spp_chunk) {
-    uint32_t cs = std::min(spp_chunk, a->spp_count - done);
+    const uint32_t cs = std::min(spp_chunk, a->spp_count - done);
     const RenderParams rp = chunk_params(c, a, pl.first, n_pix, done, cs, (uint32_t)c->q[0].cap);
     if (a->max_depth == 0) continue;  // trace(ray, 0) returns (0, 0) for every sample: nothing to add
-    // the queues, their shared work counter and the results slab
-    uint32_t* work = c->work;
-    float4* res = c->results;
-    // fork: the queues start after the accumulate that last read the slab
-    // (acc_done, on the caller's stream; the kernels read nothing else the
-    // caller's stream writes)
-    const uint32_t n0 = (uint32_t)std::min<size_t>(rp.G, c->pool_cap);
-    HIP_CHECK(hipStreamWaitEvent(c->q[0].stream, c->acc_done, 0));
-    HIP_CHECK(hipMemcpyAsync(work, &n0, 4, hipMemcpyHostToDevice, c->q[0].stream));
-    HIP_CHECK(hipEventRecord(c->set_fork, c->q[0].stream));
-    uint32_t base = 0;
-    for (int k = 0; k < K; ++k) {
-      Queue& q = c->q[k];
-      const uint32_t nk = (uint32_t)(((uint64_t)n0 * (k + 1)) / K) - base;  // <= q.cap
-      if (k) HIP_CHECK(hipStreamWaitEvent(q.stream, c->set_fork, 0));
-      Ctrl init{{nk, 0}, 0, 0};
-      HIP_CHECK(hipMemcpyAsync(q.ctrl, &init, sizeof(Ctrl), hipMemcpyHostToDevice, q.stream));
-      if (nk) {
-        hipLaunchKernelGGL(k_generate, dim3((nk + kBlock - 1) / kBlock), dim3(kBlock), 0, q.stream, c->cam, rp,
-                           q.bufs[0], base, nk);
-        HIP_CHECK(hipGetLastError());
-      }
-      base += nk;
-    }
-    std::vector<std::array<hipEvent_t, 3>> marks;
-    std::vector<std::array<hipEvent_t, 2>> fin_marks;
-    const int kBatch = 4;  // even: a status read sees the live pool in active[0]
-    struct Loop {
-      uint32_t it = 0;
-      int slot = 0;
-      bool pending = false, finished = false;
-      size_t bound = ~(size_t)0;  // live paths at most (shade_grid)
-      bool exhausted = false;     // the work counter was seen at or past G: no refill
-    } st_[kMaxQueues];
-    int open = K;
-    // an internal error in the middle of a chunk: every queue's kernels end
-    // before the error returns, so the next render does not fork onto pools
-    // and a results slab that this chunk's launches still write
-    auto fail_chunk = [&](const std::string& msg) {
-      for (int k = 0; k < K; ++k) (void)hipStreamSynchronize(c->q[k].stream);
-      throw ApiError{MRT_ERR_HIP, msg};
-    };
-    const ShadeFn shade = shade_kernel(count, c->scene_ext, c->tun.shade_wpe);
-    while (open > 0) {
-      for (int k = 0; k < K; ++k) {
-        Queue& q = c->q[k];
-        Loop& L = st_[k];
-        if (L.finished) continue;
-        for (int b = 0; b < kBatch; ++b, ++L.it) {
-          const uint32_t cur = L.it & 1;
-          std::array<hipEvent_t, 3> m{};
-          if (timing) {
-            m[0] = next_event();
-            HIP_CHECK(hipEventRecord(m[0], q.stream));
-          }
-          if (simple)
-            launch_trace_simple(c, q, cur);
-          else
-            launch_trace(c, q.stream, q, q.bufs[cur], cur, count, kTmin, INFINITY);
-          if (timing) {
-            m[1] = next_event();
-            HIP_CHECK(hipEventRecord(m[1], q.stream));
-          }
-          hipLaunchKernelGGL(shade, dim3(shade_grid(q, L.bound)), dim3(kShadeBlock), 0, q.stream, c->S, rp, q.bufs[cur],
-                             q.bufs[cur ^ 1], (const uint4*)q.hits, q.ctrl, cur, res, c->d_cnt);
-          HIP_CHECK(hipGetLastError());
-          if (!L.exhausted || rp.shade_bin == 2) {  // new paths behind the survivors (shade_bin 2: and the pool's ends joined)
-            hipLaunchKernelGGL(k_reserve, dim3(1), dim3(64), 0, q.stream, q.ctrl, cur, work, rp.G, rp.pool_cap);
-            hipLaunchKernelGGL(k_refill, dim3(c->refill_grid), dim3(kBlock), 0, q.stream, c->cam, rp, q.bufs[cur ^ 1],
-                               (const Ctrl*)q.ctrl);
-            HIP_CHECK(hipGetLastError());
-          }
-          if (timing) {
-            m[2] = next_event();
-            HIP_CHECK(hipEventRecord(m[2], q.stream));
-            marks.push_back(m);
-          }
-        }
-        hipLaunchKernelGGL(k_status, dim3(1), dim3(64), 0, q.stream, (const Ctrl*)q.ctrl, (const uint32_t*)work,
-                           q.d_stat + L.slot);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipEventRecord(q.ev[L.slot], q.stream));
-        if (L.pending) {  // the previous batch's status (one batch stays in flight)
-          HIP_CHECK(hipEventSynchronize(q.ev[L.slot ^ 1]));
-          const volatile HostStatus& v = q.h_stat[L.slot ^ 1];  // written by the GPU
-          const HostStatus s{v.active0, v.active1, v.shade_short, v.work};
-          if (s.shade_short)
-            fail_chunk("internal: a k_shade grid was smaller than its live pool (" + std::to_string(s.shade_short) +
-                       " paths)");
-          if (s.work >= rp.G) {
-            L.bound = std::min<size_t>(L.bound, s.active0);
-            L.exhausted = true;
-          }
-          if (s.work >= rp.G && s.active0 <= finish_paths) {
-            // no new work: the paths left (at most as many as that status
-            // showed) finish in one fused launch after the batch just queued
-            if (s.active0 > 0) {
-              std::array<hipEvent_t, 2> fm{};
-              if (timing) {
-                fm[0] = next_event();
-                HIP_CHECK(hipEventRecord(fm[0], q.stream));
-              }
-              launch_finish(c, k, L.it & 1, rp, count, res);
-              if (timing) {
-                fm[1] = next_event();
-                HIP_CHECK(hipEventRecord(fm[1], q.stream));
-                fin_marks.push_back(fm);
-              }
-            }
-            L.finished = true;
-            --open;
-          }
-        }
-        L.pending = true;
-        L.slot ^= 1;
-        if (L.it > 64u * 1024u) fail_chunk("render did not converge");
-      }
-    }
-    // join: `st` continues after every queue (which may still be running its
-    // drain: the host does not wait)
-    for (int k = 0; k < K; ++k) {
-      HIP_CHECK(hipEventRecord(c->q[k].join, c->q[k].stream));
-      HIP_CHECK(hipStreamWaitEvent(st, c->q[k].join, 0));
-    }
-    if (timing) {  // resolved by mrt_get_kernel_stats (resolve_kernel_timing)
-      c->pend_marks.insert(c->pend_marks.end(), marks.begin(), marks.end());
-      c->pend_fin.insert(c->pend_fin.end(), fin_marks.begin(), fin_marks.end());
-    }
-    hipLaunchKernelGGL(k_accumulate, dim3((n_pix + kAccPix - 1) / kAccPix), dim3(kBlock), 0, st, (const float4*)res,
-                       n_pix, cs, (const uint32_t*)pl.first, d_rgb, d_b);
-    HIP_CHECK(hipGetLastError());
+    fork_queues(c, rp);
+    run_queues(c, rp, p, stamps);
+    join_queues(c, st);
+    stamps.keep();
+    accumulate(c, rp, d_rgb, d_b, st);
     HIP_CHECK(hipEventRecord(c->acc_done, st));  // the slab is free again after this
   }
 }

@@ -365,7 +365,7 @@ extern "C" int mrt_trace_rays(mrt_ctx* c, const float* rays, uint32_t n, float t
     const uint32_t g = (n + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(k_rays_in, dim3(g), dim3(kBlock), 0, c->stream, (const float*)c->d_rays, n, q.bufs[0]);
     HIP_CHECK(hipGetLastError());
-    Ctrl init{{n, 0}, n, 0};
+    const Ctrl init = ctrl_init(n, /*next_work*/ n);
     HIP_CHECK(hipMemcpyAsync(q.ctrl, &init, sizeof(Ctrl), hipMemcpyHostToDevice, c->stream));
     launch_trace(c, c->stream, q, q.bufs[0], 0u, true, t_min, t_max);
     hipLaunchKernelGGL(c->scene_ext ? k_rays_out<true> : k_rays_out<false>, dim3(g), dim3(kBlock), 0, c->stream, c->S,

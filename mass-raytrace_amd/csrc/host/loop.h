@@ -1,0 +1,169 @@
+// loop.h — the integer decisions of the wavefront loop (render.hip): the
+// refill and gap-closing plan of k_reserve, the sizes of the path pool and
+// the results slab, the split of a chunk's first paths over the queues, and
+// what a queue does with a lagged status read. Plain C++, no HIP: every
+// function here runs on the host in tools/loop_check.cpp
+// (tests/test_loop.py); those a kernel also calls carry MRT_HD.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "../mrt_math.h"
+
+// Lagged status read of a queue (k_status): the fields the host loop needs.
+// (At global scope beside pool.h's Ctrl: k_status takes both.)
+struct HostStatus {
+  uint32_t active0, active1, shade_short, work;
+};
+
+namespace mrt {
+
+// ---- refill (k_reserve -> k_refill) ----------------------------------------
+
+// Work items a pool of `cap` slots with `n` survivors asks the work counter for.
+MRT_HD uint32_t refill_want(uint32_t n, uint32_t cap) { return n < cap ? cap - n : 0u; }
+
+// What k_reserve stores into Ctrl after its atomic: work items
+// [gen_base, gen_base + gen_count) go to slots [gen_slot, gen_slot +
+// gen_count) behind the survivors, gen_move paths go from gen_move_src.. to
+// gen_move_dst.., and the pool then holds `active` paths in [0, active).
+struct RefillPlan {
+  uint32_t gen_slot, gen_count, gen_base, gen_move, gen_move_src, gen_move_dst, active;
+};
+
+// The refill of a pool of `cap` slots whose survivors sit in [0, lo) and
+// (shade_bin 2) in [cap - hi, cap); `base` is what the work counter's
+// atomicAdd(refill_want) returned, or G when none was issued (nothing wanted,
+// or the counter already at or past G).
+MRT_HD RefillPlan plan_refill(uint32_t lo, uint32_t hi, uint32_t cap, uint32_t G, uint32_t base) {
+  const uint32_t n = lo + hi, want = refill_want(n, cap);
+  const uint32_t m = base < G ? (G - base < want ? G - base : want) : 0u;
+  // the top block [cap - hi, cap) closes onto the refill's end lo + m: its
+  // paths at or past the new end E move into the free slots below E
+  const uint32_t E = n + m, g = cap - E;
+  const uint32_t mv = g < hi ? g : hi;
+  // sources [cap - mv, cap) and destinations [lo + m, lo + m + mv) are
+  // disjoint, and the pool stays contiguous: [0, E) live, nothing past it
+  return RefillPlan{lo, m, base, mv, cap - mv, lo + m, E};
+}
+
+// ---- buffer sizes (plan_buffers) -------------------------------------------
+
+// device bytes of a pool of P paths over `queues` queues: two state
+// sets (5 x 16 B each) + the hit record per path, 256-B aligned sections
+constexpr size_t kPathBytes = 16 * (2 * 5 + 1);
+inline size_t pool_bytes(int queues, size_t P) {
+  const size_t K = (size_t)queues, per_q = (P + K - 1) / K;
+  return (kPathBytes * per_q + 4096) * K;
+}
+
+// the pool does not shrink below this many paths before the chunks do
+constexpr size_t kPoolFloor = (size_t)64 << 20;
+
+// The first samples per chunk of a render: results slab <= results_max
+// samples (16 B each).
+inline uint32_t first_chunk(uint32_t spp_count, uint64_t results_max, uint32_t n_pix) {
+  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(spp_count, results_max / n_pix));
+}
+
+// The pool a chunk of spp_chunk samples per pixel asks for: pool <= pool_paths.
+inline size_t pool_wanted(uint32_t n_pix, uint32_t spp_chunk, size_t pool_paths, bool need_pool) {
+  return need_pool ? std::min<size_t>((size_t)n_pix * spp_chunk, pool_paths) : 0;
+}
+
+// The pool (P paths) and the samples per results chunk that fit `budget`
+// bytes: the pool shrinks first (its size barely matters from 128M paths on,
+// DESIGN.md §4), down to kPoolFloor paths, then the samples per results chunk
+// (more chunks, the same image: chunks accumulate in sample order). !fits:
+// not even one sample per pixel fits.
+struct SizePlan {
+  size_t P;
+  uint32_t spp_chunk;
+  bool fits;
+};
+inline SizePlan plan_sizes(uint32_t n_pix, uint32_t spp_chunk, size_t pool_paths, int queues, size_t budget,
+                           bool need_pool) {
+  size_t P = pool_wanted(n_pix, spp_chunk, pool_paths, need_pool);
+  for (;;) {
+    const size_t need = (P ? pool_bytes(queues, P) : 0) + (size_t)n_pix * spp_chunk * 16;
+    if (need <= budget) return SizePlan{P, spp_chunk, true};
+    if (P > kPoolFloor) {
+      P = std::max(kPoolFloor, P / 2);
+    } else if (spp_chunk > 1) {
+      spp_chunk = spp_chunk / 2;
+      if (P) P = std::min<size_t>(P, (size_t)n_pix * spp_chunk);
+    } else {
+      return SizePlan{P, spp_chunk, false};
+    }
+  }
+}
+
+// ---- the fork ---------------------------------------------------------------
+
+// Queue k's share of a chunk's first n0 paths over K queues (<= ceil(P / K),
+// the queue's capacity, for n0 <= the pool's P); the shares before it sum to
+// its first work item.
+inline uint32_t queue_share(uint32_t n0, int K, int k) {
+  return (uint32_t)(((uint64_t)n0 * (k + 1)) / K) - (uint32_t)(((uint64_t)n0 * k) / K);
+}
+
+// ---- the per-queue loop -----------------------------------------------------
+
+// k_shade's grid for a pool of `cap` slots known to hold at most `bound`
+// live paths: one workgroup per `block` of them.
+// While the work counter has items left the pool refills to capacity; once
+// it is exhausted the live count only falls, so the last status the host
+// read bounds every later launch — a drain launch then dispatches a few
+// workgroups instead of one per 256 slots of the whole pool.
+inline uint32_t shade_workgroups(size_t cap, size_t bound, uint32_t block) {
+  const size_t n = std::min(cap, bound);
+  return (uint32_t)std::max<size_t>(1, (n + block - 1) / block);
+}
+
+// Iterations (k_trace + k_shade + refill) a queue enqueues between two status
+// reads. Even: a status read sees the live pool in active[0].
+constexpr int kBatch = 4;
+static_assert(kBatch % 2 == 0, "on_status reads the live pool from active0");
+
+// A queue that ran this many iterations did not converge.
+constexpr uint32_t kMaxIterations = 64u * 1024u;
+
+// One queue's state in the host loop.
+struct QueueLoop {
+  uint32_t it = 0;
+  int slot = 0;
+  bool pending = false, finished = false;
+  size_t bound = ~(size_t)0;  // live paths at most (shade_workgroups)
+  bool exhausted = false;     // the work counter was seen at or past G: no refill
+};
+
+// What a queue does after a status read.
+enum class LoopStep {
+  kGoOn,        // enqueue the next batch
+  kHandOff,     // finished: the paths left go to one fused launch (launch_finish)
+  kFinished,    // finished: no path left (or no hand-off and none left)
+  kShadeShort,  // fail: a k_shade grid was smaller than its live pool
+};
+
+// The status `s` of the batch before the one just queued, for a chunk of G
+// work items: once the counter is exhausted the status bounds the live count
+// (shade_workgroups) and the refill stops; then, with at most finish_paths
+// paths left, the queue finishes — no new work: the paths left (at most as
+// many as that status showed) finish in one fused launch after the batch
+// just queued.
+inline LoopStep on_status(QueueLoop& L, const HostStatus& s, uint32_t G, uint32_t finish_paths) {
+  if (s.shade_short) return LoopStep::kShadeShort;
+  if (s.work >= G) {
+    L.bound = std::min<size_t>(L.bound, s.active0);
+    L.exhausted = true;
+  }
+  if (s.work >= G && s.active0 <= finish_paths) {
+    L.finished = true;
+    return s.active0 > 0 ? LoopStep::kHandOff : LoopStep::kFinished;
+  }
+  return LoopStep::kGoOn;
+}
+
+}  // namespace mrt
