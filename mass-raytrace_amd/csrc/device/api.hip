@@ -45,7 +45,7 @@ void apply_options(mrt_ctx* c) {
 void set_option(mrt_ctx* c, int id, int64_t v) {
   const std::string why = opt_invalid(id, v);
   if (!why.empty()) throw ApiError{MRT_ERR_INVALID, why};
-  if (id == OPT_QUEUES && v != c->opt[id] && c->pool_mem) {  // the pool is split per queue: reallocated at the next render
+  if (id == OPT_QUEUES && v != c->opt[id] && c->pool.p) {  // the pool is split per queue: reallocated at the next render
     HIP_CHECK(hipDeviceSynchronize());
     release_pool(c);
     c->grids.clear();  // k_trace's grid share depends on the queue count
@@ -85,7 +85,7 @@ int mrt_create(int device, mrt_ctx** out) {
     for (int k = 0; k < kMaxQueues; ++k) {
       Queue& q = c->q[k];
       HIP_CHECK(hipStreamCreateWithFlags(&q.stream, hipStreamNonBlocking));
-      HIP_CHECK(hipMalloc(&q.ctrl, sizeof(Ctrl)));
+      HIP_CHECK(q.ctrl.alloc(1));
       HIP_CHECK(hipHostMalloc(&q.h_stat, 2 * sizeof(HostStatus), hipHostMallocCoherent | hipHostMallocMapped));
       memset(q.h_stat, 0, 2 * sizeof(HostStatus));
       HIP_CHECK(hipHostGetDevicePointer((void**)&q.d_stat, q.h_stat, 0));
@@ -93,14 +93,14 @@ int mrt_create(int device, mrt_ctx** out) {
       HIP_CHECK(hipEventCreateWithFlags(&q.ev[1], hipEventDisableTiming));
       HIP_CHECK(hipEventCreateWithFlags(&q.join, hipEventDisableTiming));
     }
-    HIP_CHECK(hipMalloc(&c->work, 256));
-    HIP_CHECK(hipMemset(c->work, 0, 256));
+    HIP_CHECK(c->work.alloc(64));  // one 256-byte line
+    HIP_CHECK(hipMemset(c->work.p, 0, 256));
     HIP_CHECK(hipEventCreateWithFlags(&c->acc_done, hipEventDisableTiming));
     HIP_CHECK(hipEventCreateWithFlags(&c->set_fork, hipEventDisableTiming));
-    HIP_CHECK(hipMalloc(&c->d_cnt, sizeof(DevCounters)));
-    HIP_CHECK(hipMemset(c->d_cnt, 0, sizeof(DevCounters)));
-    HIP_CHECK(hipMalloc(&c->dbg, 16));
-    HIP_CHECK(hipMemset(c->dbg, 0, 16));
+    HIP_CHECK(c->d_cnt.alloc(1));
+    HIP_CHECK(hipMemset(c->d_cnt.p, 0, sizeof(DevCounters)));
+    HIP_CHECK(c->dbg.alloc(4));
+    HIP_CHECK(hipMemset(c->dbg.p, 0, 16));
     HIP_CHECK(hipEventCreate(&c->tev[0]));
     HIP_CHECK(hipEventCreate(&c->tev[1]));
     int cus = 0;
@@ -134,34 +134,19 @@ int mrt_destroy(mrt_ctx* c) {
   if (c->stream) hipStreamSynchronize(c->stream);
   for (Queue& q : c->q)
     if (q.stream) hipStreamSynchronize(q.stream);
-  hipFree(c->scene_mem);
-  hipFree(c->pool_mem);
-  hipFree(c->results);
   if (c->acc_done) hipEventDestroy(c->acc_done);
   if (c->set_fork) hipEventDestroy(c->set_fork);
-  hipFree(c->work);
-  hipFree(c->gamma_d);
   for (Queue& q : c->q) {
-    hipFree(q.ctrl);
     if (q.h_stat) hipHostFree(q.h_stat);
     for (hipEvent_t e : {q.ev[0], q.ev[1], q.join})
       if (e) hipEventDestroy(e);
     if (q.stream) hipStreamDestroy(q.stream);
   }
-  hipFree(c->d_cnt);
-  hipFree(c->dbg);
-  hipFree(c->d_acc_rgb);
-  hipFree(c->d_acc_b);
-  hipFree(c->d_rays);
-  hipFree(c->d_rhits);
-  hipFree(c->dn_mem);
-  hipFree(c->slot_ro);
-  for (auto& kv : c->pixlists) hipFree(kv.second.first);
   if (c->tev[0]) hipEventDestroy(c->tev[0]);
   if (c->tev[1]) hipEventDestroy(c->tev[1]);
   for (hipEvent_t e : c->ev_pool) hipEventDestroy(e);
   if (c->stream) hipStreamDestroy(c->stream);
-  delete c;
+  delete c;  // the device buffers free themselves (devmem.h), on c->device
   return MRT_OK;
 }
 
@@ -183,85 +168,23 @@ int mrt_upload_scene_targets(mrt_ctx* c, const mrt_scene_desc* d, const mrt_scen
                   : c->opt[OPT_TRAVERSAL] == MRT_TRAVERSAL_NEAR_FIRST ? kNfBuildAlways : kNfBuildAuto;
     if (!build_host_scene(*d, hs, err, true, ext, targets, n_targets)) throw ApiError{MRT_ERR_INVALID, err};
     build_treelet(hs, (uint32_t)((size_t)c->tun.treelet_kb * 1024 / 16));
-    // one allocation, 256-B aligned sections
-    size_t off = 0;
-    auto sec = [&](size_t bytes) {
-      size_t o = off;
-      off += (bytes + 255) & ~(size_t)255;
-      return o;
-    };
-    size_t o_slots = sec(hs.slots.size() * 4), o_stl = sec(hs.slots_tl.size() * 4), o_tlet = sec(hs.tlet.size() * 4),
-           o_inv = sec(hs.inst_inv.size() * 4),
-           o_fwd = sec(hs.inst_fwd.size() * 4), o_imat = sec(hs.inst_mat.size() * 4),
-           o_mmat = sec(hs.model_mat.size() * 4), o_sph = sec(hs.sph.size() * 4), o_smat = sec(hs.sph_mat.size() * 4),
-           o_tri = sec(hs.tri_shade.size() * 4), o_mat = sec(hs.materials.size() * sizeof(GpuMaterial)),
-           o_tex = sec(hs.textures.size() * sizeof(GpuTexture)), o_texel = sec(hs.texels.size() * 4),
-           o_vnid = sec(hs.vol_nid.size() * 4), o_vmat = sec(hs.vol_mat.size() * 4);
-    const std::vector<float>& ln_table = hs.ln_table;
-    const size_t o_ln = sec(ln_table.size() * 4);
-    const size_t o_sops = sec(hs.surf_ops.size() * sizeof(GpuSurfOp));
-    const size_t o_bgf = sec(hs.bg_faces.size() * sizeof(GpuSurfRef));
-    const size_t o_bgm = sec(sizeof(hs.bg_m));
-    const size_t o_vnf = sec(hs.vnf_leaf.size() * 4);
-    const size_t o_eve = sec(hs.eve.size() * 4), o_tb = sec(hs.tri_tb.size() * 4);
-    if (c->scene_mem) HIP_CHECK(hipFree(c->scene_mem));
-    c->scene_mem = nullptr;
+    // one allocation, 256-B aligned sections (upload.h: the arrays' list and their placement)
+    const ScenePlan plan = plan_scene(hs);
+    HIP_CHECK(c->scene.free());
     c->has_scene = false;
-    HIP_CHECK(hipMalloc(&c->scene_mem, off + 256));
-    char* base = (char*)c->scene_mem;
-    auto up = [&](size_t o, const void* src, size_t bytes) {
-      if (bytes) HIP_CHECK(hipMemcpy(base + o, src, bytes, hipMemcpyHostToDevice));
-    };
-    up(o_slots, hs.slots.data(), hs.slots.size() * 4);
-    up(o_stl, hs.slots_tl.data(), hs.slots_tl.size() * 4);
-    up(o_tlet, hs.tlet.data(), hs.tlet.size() * 4);
-    up(o_vnid, hs.vol_nid.data(), hs.vol_nid.size() * 4);
-    up(o_vmat, hs.vol_mat.data(), hs.vol_mat.size() * 4);
-    up(o_ln, ln_table.data(), ln_table.size() * 4);
-    up(o_inv, hs.inst_inv.data(), hs.inst_inv.size() * 4);
-    up(o_fwd, hs.inst_fwd.data(), hs.inst_fwd.size() * 4);
-    up(o_imat, hs.inst_mat.data(), hs.inst_mat.size() * 4);
-    up(o_mmat, hs.model_mat.data(), hs.model_mat.size() * 4);
-    up(o_sph, hs.sph.data(), hs.sph.size() * 4);
-    up(o_smat, hs.sph_mat.data(), hs.sph_mat.size() * 4);
-    up(o_tri, hs.tri_shade.data(), hs.tri_shade.size() * 4);
-    up(o_mat, hs.materials.data(), hs.materials.size() * sizeof(GpuMaterial));
-    up(o_tex, hs.textures.data(), hs.textures.size() * sizeof(GpuTexture));
-    up(o_texel, hs.texels.data(), hs.texels.size() * 4);
-    up(o_sops, hs.surf_ops.data(), hs.surf_ops.size() * sizeof(GpuSurfOp));
-    up(o_bgf, hs.bg_faces.data(), hs.bg_faces.size() * sizeof(GpuSurfRef));
-    up(o_bgm, hs.bg_m, sizeof(hs.bg_m));
-    up(o_vnf, hs.vnf_leaf.data(), hs.vnf_leaf.size() * 4);
-    up(o_eve, hs.eve.data(), hs.eve.size() * 4);
-    up(o_tb, hs.tri_tb.data(), hs.tri_tb.size() * 4);
+    HIP_CHECK(c->scene.alloc(plan.total + 256));
     DevScene S = host_dev_scene(hs);  // sizes and flags; its pointers now go to the device copies
-    S.slots = (const uint32_t*)(base + o_slots);
-    S.slots_tl = (const uint32_t*)(base + o_stl);
-    S.tlet = (const uint32_t*)(base + o_tlet);
+    size_t k = 0;
+    for_each_scene_array(hs, [&](auto field, auto* src, size_t bytes, unsigned flags) {
+      char* dst = c->scene.p + plan.off[k++];
+      if (bytes) HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+      S.*field = bytes || !(flags & kArrNullIfEmpty) ? (decltype(src))dst : nullptr;
+    });
     S.n_tlet = (uint32_t)(hs.tlet.size() / 4);
     S.tl_world_begin = hs.tl_world_begin;
-    S.inst_inv = (const float*)(base + o_inv);
-    S.inst_fwd = (const float*)(base + o_fwd);
-    S.inst_mat = (const uint32_t*)(base + o_imat);
-    S.model_mat = (const uint32_t*)(base + o_mmat);
-    S.sph = (const float*)(base + o_sph);
-    S.sph_mat = (const uint32_t*)(base + o_smat);
-    S.tri_shade = (const float*)(base + o_tri);
-    S.materials = (const GpuMaterial*)(base + o_mat);
-    S.textures = (const GpuTexture*)(base + o_tex);
-    S.texels = (const uint32_t*)(base + o_texel);
-    S.vol_nid = (const float*)(base + o_vnid);
-    S.vol_mat = (const uint32_t*)(base + o_vmat);
-    S.ln_table = ln_table.empty() ? nullptr : (const float*)(base + o_ln);
-    S.dbg = c->dbg;
-    S.surf_ops = (const GpuSurfOp*)(base + o_sops);
-    S.bg_faces = (const GpuSurfRef*)(base + o_bgf);
-    S.bg_m = (const float*)(base + o_bgm);
-    S.vnf_leaf = (const uint32_t*)(base + o_vnf);
-    S.eve = (const float*)(base + o_eve);
-    S.tri_tb = hs.tri_tb.empty() ? nullptr : (const float*)(base + o_tb);
+    S.dbg = c->dbg.p;
     c->S = S;
-    c->scene_bytes = off;
+    c->scene_bytes = plan.total;
     // the reference stream's size decides the per-scene rules (the NF trees follow it)
     c->facts.big = (size_t)hs.nf_first_slot * 16 > ((size_t)16 << 20);
     c->facts.instances = S.n_inst;
@@ -371,7 +294,7 @@ int mrt_get_counters(mrt_ctx* c, mrt_counters* out) {
     HIP_CHECK(hipStreamSynchronize(c->stream));
     HIP_CHECK(hipDeviceSynchronize());
     DevCounters h;
-    HIP_CHECK(hipMemcpy(&h, c->d_cnt, sizeof(h), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&h, c->d_cnt.p, sizeof(h), hipMemcpyDeviceToHost));
     out->samples = h.samples;
     out->segments = h.segments;
     out->node_visits = h.node_visits;
@@ -397,7 +320,7 @@ int mrt_reset_counters(mrt_ctx* c) {
   MRT_EACH(c, mrt_reset_counters(c));
   return guarded(c, [&] {
     HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemset(c->d_cnt, 0, sizeof(DevCounters)));
+    HIP_CHECK(hipMemset(c->d_cnt.p, 0, sizeof(DevCounters)));
   });
 }
 
@@ -435,7 +358,7 @@ int mrt_debug_status(mrt_ctx* c, uint32_t* out4) {
   return guarded(c, [&] {
     if (!out4) throw ApiError{MRT_ERR_INVALID, "null output"};
     HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(out4, c->dbg, 16, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(out4, c->dbg.p, 16, hipMemcpyDeviceToHost));
   });
 }
 
@@ -450,7 +373,7 @@ int mrt_debug_build(void) {
 int mrt_shard_pixels(uint32_t W, uint32_t H, uint32_t si, uint32_t sc, uint32_t* pixels, uint32_t* count) {
   try {
     if (!count) throw ApiError{MRT_ERR_INVALID, "null count"};
-    if (W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 32)) throw ApiError{MRT_ERR_INVALID, "bad image size"};
+    check_image_size(W, H);
     if (sc == 0) sc = 1;
     if (si >= sc) throw ApiError{MRT_ERR_INVALID, "shard_index >= shard_count"};
     const std::vector<uint32_t> list = shard_pixel_list(W, H, si, sc);

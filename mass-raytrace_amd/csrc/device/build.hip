@@ -14,6 +14,7 @@
 #include <string>
 
 #include "build.h"
+#include "devmem.h"
 
 namespace massrt {
 namespace {
@@ -150,19 +151,6 @@ __global__ __launch_bounds__(kBuildBlock) void k_iota(uint32_t* perm, uint32_t n
   if (i < n) perm[i] = i;
 }
 
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  explicit DevBuf(size_t n) {
-    if (n) BUILD_CHECK(hipMalloc(&p, n * sizeof(T)));
-  }
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-};
-
 uint32_t grid_for(size_t n) { return (uint32_t)((n + kBuildBlock - 1) / kBuildBlock); }
 
 }  // namespace
@@ -239,13 +227,16 @@ void device_build_tree(int device, const std::vector<Item>& items, mrt::WyRand& 
   }
   size_t total_segs = 0;
   for (auto& s : segs) total_segs += s.size();
-  DevBuf<float> d_box(6 * n), d_nbox(6 * (size_t)T);
-  DevBuf<uint32_t> d_perm(n), d_perm2(n), d_level_nodes(T), d_nan(1);
-  DevBuf<unsigned long long> d_keys(n), d_keys2(n);
-  DevBuf<Seg> d_segs(total_segs ? total_segs : 1);
-  DevBuf<NodeRange> d_range(T);
-  DevBuf<uint32_t> d_ref(n);
-  DevBuf<mrt_node> d_out(T);
+  DevBuf<float> d_box, d_nbox;
+  DevBuf<uint32_t> d_perm, d_perm2, d_level_nodes, d_nan, d_ref;
+  DevBuf<unsigned long long> d_keys, d_keys2;
+  DevBuf<Seg> d_segs;
+  DevBuf<NodeRange> d_range;
+  DevBuf<mrt_node> d_out;
+  auto need = [](auto& buf, size_t count) { BUILD_CHECK(buf.alloc(count)); };
+  need(d_box, 6 * n), need(d_nbox, 6 * (size_t)T), need(d_perm, n), need(d_perm2, n), need(d_level_nodes, T);
+  need(d_nan, 1), need(d_keys, n), need(d_keys2, n), need(d_segs, total_segs ? total_segs : 1);
+  need(d_range, T), need(d_ref, n), need(d_out, T);
   BUILD_CHECK(hipMemcpyAsync(d_box.p, hb.data(), hb.size() * 4, hipMemcpyHostToDevice, st));
   BUILD_CHECK(hipMemcpyAsync(d_ref.p, href.data(), n * 4, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_iota, dim3(grid_for(n)), dim3(kBuildBlock), 0, st, d_perm.p, (uint32_t)n);
@@ -266,7 +257,8 @@ void device_build_tree(int device, const std::vector<Item>& items, mrt::WyRand& 
   size_t temp_bytes = 0;
   BUILD_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, d_keys.p, d_keys2.p, d_perm.p, d_perm2.p,
                                                  (int)n, 0, end_bit, st));
-  DevBuf<char> d_temp(temp_bytes ? temp_bytes : 1);
+  DevBuf<char> d_temp;
+  BUILD_CHECK(d_temp.alloc(temp_bytes ? temp_bytes : 1));
   uint32_t* perm = d_perm.p;
   uint32_t* perm_alt = d_perm2.p;
   for (uint32_t l = 0; l < L; ++l) {

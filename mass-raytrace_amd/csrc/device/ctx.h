@@ -16,6 +16,7 @@
 #include "../../../include/massrt.h"
 #include "../host/loop.h"
 #include "../host/options.h"
+#include "devmem.h"
 #include "frames.h"
 #include "pool.h"
 
@@ -33,16 +34,20 @@ struct ApiError {
   std::string msg;
 };
 
+inline void check_image_size(uint32_t W, uint32_t H) {
+  if (W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 32)) throw ApiError{MRT_ERR_INVALID, "bad image size"};
+}
+
 // One independent path pool driven on its own stream. Several queues share
 // the work counter and run concurrently, so one queue's k_trace tail (the
 // last long rays on few lanes) overlaps the other queues' kernels instead of
 // idling the GPU.
 struct Queue {
   hipStream_t stream = nullptr;
-  PathBufs bufs[2]{};
+  PathBufs bufs[2]{};   // views into the context's pool, as is hits
   uint4* hits = nullptr;
-  size_t cap = 0;
-  Ctrl* ctrl = nullptr;        // device
+  size_t cap = 0;       // paths
+  DevBuf<Ctrl> ctrl;
   HostStatus* h_stat = nullptr;  // pinned coherent, 2 slots, written by k_status (lagged status reads)
   HostStatus* d_stat = nullptr;  // the same memory as the device addresses it
   hipEvent_t ev[2]{};
@@ -56,8 +61,8 @@ struct mrt_ctx {
   hipStream_t stream = nullptr;
   std::string err;
   // scene
-  void* scene_mem = nullptr;
-  size_t scene_bytes = 0;
+  DevBuf<char> scene;      // every array of S, one allocation (upload.h plan_scene)
+  size_t scene_bytes = 0;  // the sections alone (mrt_scene_device_bytes)
   mrt::DevScene S{};
   bool has_scene = false;
   mrt::DevCamera cam{};
@@ -72,12 +77,11 @@ struct mrt_ctx {
   bool scene_ext = false;   // composite surfaces, a CubeMap background or Eve materials (the EXT kernel variants)
   // render state
   size_t pool_cap = 0;  // paths over all queues
-  void* pool_mem = nullptr;
+  DevBuf<char> pool;
   Queue q[mrt::kMaxQueues];
-  uint32_t* work = nullptr;    // shared work counter of the wavefront loop (word 1: tonemap max count)
-  uint32_t* gamma_d = nullptr; // display: gamma byte thresholds (256 words)
-  float4* results = nullptr;  // the results slab (results_cap samples)
-  size_t results_cap = 0;
+  DevBuf<uint32_t> work;     // shared work counter of the wavefront loop (word 1: tonemap max count)
+  DevBuf<uint32_t> gamma_d;  // display: gamma byte thresholds (256 words)
+  DevBuf<float4> results;    // the results slab, one float4 per sample
   // acc_done: recorded on the caller's stream after the accumulate that read
   // the results slab (and after any other caller-stream work on the shared
   // buffers, mark_ctx_busy); the next render's queues fork after it.
@@ -89,34 +93,32 @@ struct mrt_ctx {
   // render does not wait for its set's drain
   std::vector<std::array<hipEvent_t, 3>> pend_marks;
   std::vector<std::array<hipEvent_t, 2>> pend_fin;
-  mrt::DevCounters* d_cnt = nullptr;
-  uint32_t* dbg = nullptr;  // MRT_DEBUG_BOUNDS record (4 words)
+  DevBuf<mrt::DevCounters> d_cnt;
+  DevBuf<uint32_t> dbg;  // MRT_DEBUG_BOUNDS record (4 words)
   int cus = 1;
   uint32_t trace_grid = 1024;   // k_trace_simple workgroups (cus * 4)
   uint32_t refill_grid = 2048;  // k_refill workgroups (grid-stride; cus * 8)
   std::map<std::pair<const void*, size_t>, uint32_t> grids;  // persistent grid per (kernel, LDS bytes)
-  // k_render: per-lane current world ray; event pair timing one launch
+  // k_render: per-lane current world ray, origins then directions in one
+  // buffer (ensure_slots sets the two views); event pair timing one launch
+  DevBuf<float4> slots;
   float4* slot_ro = nullptr;
   float4* slot_rd = nullptr;
-  size_t slots_cap = 0;
   hipEvent_t tev[2] = {nullptr, nullptr};
 
-  std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>, std::pair<uint32_t*, uint32_t>> pixlists;
+  std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>, DevBuf<uint32_t>> pixlists;
   // host-buffer render staging
-  float* d_acc_rgb = nullptr;
-  uint32_t* d_acc_b = nullptr;
-  size_t acc_cap = 0;
+  DevBuf<float> d_acc_rgb;
+  DevBuf<uint32_t> d_acc_b;
   // kernel timing
   std::vector<hipEvent_t> ev_pool;
   size_t ev_used = 0;
   mrt_kernel_stats kstats{};
   // device ray buffer for mrt_trace_rays
-  float* d_rays = nullptr;
-  uint4* d_rhits = nullptr;
-  size_t rays_cap = 0;
+  DevBuf<float> d_rays;
+  DevBuf<uint4> d_rhits;
   // denoise.hip scratch: colour A, colour B (one float4 per pixel each), guides (two float4 per pixel)
-  float4* dn_mem = nullptr;
-  size_t dn_cap = 0;  // pixels
+  DevBuf<float4> dn_mem;
 };
 
 // errors without a context (api.hip); not exported from the library

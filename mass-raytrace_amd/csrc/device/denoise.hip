@@ -210,7 +210,7 @@ float dn_inv(float sigma, bool& on) {
 
 void denoise_check(uint32_t W, uint32_t H, const float* rgb, const float* albedo, const float* normal,
                    const mrt_denoise_params* params, const float* out) {
-  if (W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 32)) throw ApiError{MRT_ERR_INVALID, "bad image size"};
+  check_image_size(W, H);
   if (!rgb || !out) throw ApiError{MRT_ERR_INVALID, "null buffer"};
   if ((albedo == nullptr) != (normal == nullptr))
     throw ApiError{MRT_ERR_INVALID, "albedo and normal go together: both or neither"};
@@ -264,13 +264,8 @@ int mrt_denoise_device(mrt_ctx* c, uint32_t W, uint32_t H, const float* d_rgb, u
       HIP_CHECK(hipGetLastError());
       return;
     }
-    if (c->dn_cap < n) {  // grows on demand, reused across calls, freed in mrt_destroy
-      if (c->dn_mem) HIP_CHECK(hipFree(c->dn_mem));
-      c->dn_mem = nullptr, c->dn_cap = 0;
-      HIP_CHECK(hipMalloc(&c->dn_mem, n * 64));
-      c->dn_cap = n;
-    }
-    float4 *colA = c->dn_mem, *colB = colA + n, *guides = colB + n;
+    HIP_CHECK(c->dn_mem.reserve(4 * n));  // grows on demand, reused across calls
+    float4 *colA = c->dn_mem.p, *colB = colA + n, *guides = colB + n;
     const bool aux = d_albedo != nullptr;
     if (aux)
       hipLaunchKernelGGL(k_denoise_prep<true>, grid, block, 0, st, W, H, tiles_x, tiles, d_rgb, scale, d_albedo,
@@ -308,28 +303,19 @@ int mrt_denoise(mrt_ctx* c, uint32_t W, uint32_t H, const float* rgb, uint32_t p
   return guarded(c, [&] {
     denoise_check(W, H, rgb, albedo, normal, params, out);
     const size_t n = (size_t)W * H;
-    float* d = nullptr;
-    HIP_CHECK(hipMalloc(&d, n * 12 * (albedo ? 4 : 2)));
-    float *d_rgb = d, *d_out = d + 3 * n, *d_albedo = albedo ? d + 6 * n : nullptr,
-          *d_normal = albedo ? d + 9 * n : nullptr;
-    int rc = MRT_OK;
-    try {
-      HIP_CHECK(hipMemcpyAsync(d_rgb, rgb, n * 12, hipMemcpyHostToDevice, c->stream));
-      if (albedo) {
-        HIP_CHECK(hipMemcpyAsync(d_albedo, albedo, n * 12, hipMemcpyHostToDevice, c->stream));
-        HIP_CHECK(hipMemcpyAsync(d_normal, normal, n * 12, hipMemcpyHostToDevice, c->stream));
-      }
-      rc = mrt_denoise_device(c, W, H, d_rgb, passes, d_albedo, d_normal, params, d_out, c->stream);
-      if (rc == MRT_OK) {
-        HIP_CHECK(hipMemcpyAsync(out, d_out, n * 12, hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK(hipStreamSynchronize(c->stream));
-      }
-    } catch (...) {
-      hipFree(d);
-      throw;
+    DevBuf<float> d;
+    HIP_CHECK(d.alloc(n * 3 * (albedo ? 4 : 2)));
+    float *d_rgb = d.p, *d_out = d.p + 3 * n, *d_albedo = albedo ? d.p + 6 * n : nullptr,
+          *d_normal = albedo ? d.p + 9 * n : nullptr;
+    HIP_CHECK(hipMemcpyAsync(d_rgb, rgb, n * 12, hipMemcpyHostToDevice, c->stream));
+    if (albedo) {
+      HIP_CHECK(hipMemcpyAsync(d_albedo, albedo, n * 12, hipMemcpyHostToDevice, c->stream));
+      HIP_CHECK(hipMemcpyAsync(d_normal, normal, n * 12, hipMemcpyHostToDevice, c->stream));
     }
-    hipFree(d);
+    const int rc = mrt_denoise_device(c, W, H, d_rgb, passes, d_albedo, d_normal, params, d_out, c->stream);
     if (rc != MRT_OK) throw ApiError{rc, c->err};
+    HIP_CHECK(hipMemcpyAsync(out, d_out, n * 12, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
   });
 }
 

@@ -33,6 +33,7 @@
 #include <thread>
 #include <vector>
 
+#include "devmem.h"
 #include "frames.h"
 
 int massrt_ctx_device(const mrt_ctx* ctx);  // api.hip
@@ -115,12 +116,12 @@ struct DevFrame {
   int device = 0;
   hipStream_t st = nullptr;
   hipEvent_t ev = nullptr;
-  float* rgb = nullptr;
-  uint32_t* b = nullptr;
-  void* slab = nullptr;
+  DevBuf<float> rgb;
+  DevBuf<uint32_t> b;
+  DevBuf<char> slab;
   uint32_t count = 0;  // pixels of this device's shard
   std::vector<uint32_t> pix;  // their indices, in slab order (host; mrt_render's per-shard upload)
-  void* recv = nullptr;  // on device 0
+  DevBuf<char> recv;  // on device 0
   // timing events around this device's renders not yet added to render_ms
   // (mrt_image_device_stats collects them; a render never waits for them)
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
@@ -171,25 +172,25 @@ struct Frame {
       HIPF(hipSetDevice(f.device));
       HIPF(hipStreamCreateWithFlags(&f.st, hipStreamNonBlocking));
       HIPF(hipEventCreateWithFlags(&f.ev, hipEventDisableTiming));
-      HIPF(hipMalloc(&f.rgb, npix() * 12));
-      HIPF(hipMalloc(&f.b, npix() * 4));
+      HIPF(f.rgb.alloc(npix() * 3));
+      HIPF(f.b.alloc(npix()));
       if (d.size() > 1) {
         MRTF(f.ctx, mrt_shard_pixels(W, H, shard(i), shards(), nullptr, &f.count));
         f.pix.resize(f.count);
         if (f.count) MRTF(f.ctx, mrt_shard_pixels(W, H, shard(i), shards(), f.pix.data(), &f.count));
-        HIPF(hipMalloc(&f.slab, (size_t)f.count * 16 + 16));
+        HIPF(f.slab.alloc((size_t)f.count * 16 + 16));
       }
     }
     HIPF(hipSetDevice(d[0].device));
-    for (size_t i = 1; i < d.size(); ++i) HIPF(hipMalloc(&d[i].recv, (size_t)d[i].count * 16 + 16));
+    for (size_t i = 1; i < d.size(); ++i) HIPF(d[i].recv.alloc((size_t)d[i].count * 16 + 16));
     clear();
   }
 
   void clear() {
     for (DevFrame& f : d) {
       HIPF(hipSetDevice(f.device));
-      HIPF(hipMemsetAsync(f.rgb, 0, npix() * 12, f.st));
-      HIPF(hipMemsetAsync(f.b, 0, npix() * 4, f.st));
+      HIPF(hipMemsetAsync(f.rgb.p, 0, npix() * 12, f.st));
+      HIPF(hipMemsetAsync(f.b.p, 0, npix() * 4, f.st));
     }
   }
 
@@ -200,14 +201,14 @@ struct Frame {
     }
     for (DevFrame& f : d) {
       hipSetDevice(f.device);
-      hipFree(f.rgb), hipFree(f.b), hipFree(f.slab);
+      (void)f.rgb.free(), (void)f.b.free(), (void)f.slab.free();
       if (f.ev) hipEventDestroy(f.ev);
       for (auto& e : f.pending) hipEventDestroy(e.first), hipEventDestroy(e.second);
       if (f.st) hipStreamDestroy(f.st);
     }
     if (!d.empty()) {
       hipSetDevice(d[0].device);
-      for (DevFrame& f : d) hipFree(f.recv);
+      for (DevFrame& f : d) (void)f.recv.free();
     }
     d.clear();
   }
@@ -226,7 +227,7 @@ struct Frame {
       HIPF(hipEventCreate(&e1));
       f.pending.push_back({e0, e1});
       HIPF(hipEventRecord(e0, f.st));
-      MRTF(f.ctx, mrt_render_device(f.ctx, &a, f.rgb, f.b, f.st));
+      MRTF(f.ctx, mrt_render_device(f.ctx, &a, f.rgb.p, f.b.p, f.st));
       HIPF(hipSetDevice(f.device));
       HIPF(hipEventRecord(e1, f.st));
     };
@@ -306,7 +307,7 @@ void Frame::gather() {
   if (d.size() < 2) return;
   const auto t0 = std::chrono::steady_clock::now();
   for (size_t i = 1; i < d.size(); ++i)
-    if (d[i].count) MRTF(d[i].ctx, mrt_shard_pack_device(d[i].ctx, W, H, shard(i), shards(), d[i].rgb, d[i].b, d[i].slab, d[i].st));
+    if (d[i].count) MRTF(d[i].ctx, mrt_shard_pack_device(d[i].ctx, W, H, shard(i), shards(), d[i].rgb.p, d[i].b.p, d[i].slab.p, d[i].st));
   uint64_t bytes = 0;
   if (m && m->rccl) {
     ensure_comms(m);
@@ -314,8 +315,8 @@ void Frame::gather() {
     NCCLF(R.group_start());
     for (size_t i = 1; i < d.size(); ++i) {
       if (!d[i].count) continue;
-      NCCLF(R.send(d[i].slab, (size_t)d[i].count * 4, ncclUint32, 0, m->comms[i], d[i].st));
-      NCCLF(R.recv(d[i].recv, (size_t)d[i].count * 4, ncclUint32, (int)i, m->comms[0], d[0].st));
+      NCCLF(R.send(d[i].slab.p, (size_t)d[i].count * 4, ncclUint32, 0, m->comms[i], d[i].st));
+      NCCLF(R.recv(d[i].recv.p, (size_t)d[i].count * 4, ncclUint32, (int)i, m->comms[0], d[0].st));
       bytes += (uint64_t)d[i].count * 16;
     }
     NCCLF(R.group_end());
@@ -326,13 +327,13 @@ void Frame::gather() {
       HIPF(hipEventRecord(d[i].ev, d[i].st));
       HIPF(hipSetDevice(d[0].device));
       HIPF(hipStreamWaitEvent(d[0].st, d[i].ev, 0));
-      HIPF(hipMemcpyPeerAsync(d[i].recv, d[0].device, d[i].slab, d[i].device, (size_t)d[i].count * 16, d[0].st));
+      HIPF(hipMemcpyPeerAsync(d[i].recv.p, d[0].device, d[i].slab.p, d[i].device, (size_t)d[i].count * 16, d[0].st));
       bytes += (uint64_t)d[i].count * 16;
     }
   }
   for (size_t i = 1; i < d.size(); ++i)
     if (d[i].count)
-      MRTF(d[0].ctx, mrt_shard_unpack_device(d[0].ctx, W, H, shard(i), shards(), d[i].recv, d[0].rgb, d[0].b, d[0].st));
+      MRTF(d[0].ctx, mrt_shard_unpack_device(d[0].ctx, W, H, shard(i), shards(), d[i].recv.p, d[0].rgb.p, d[0].b.p, d[0].st));
   HIPF(hipSetDevice(d[0].device));
   HIPF(hipStreamSynchronize(d[0].st));
   gather_bytes += bytes;
@@ -420,8 +421,8 @@ int multi_render(MultiDev* m, const mrt_render_args* a, float* rgb, uint32_t* bo
             DevFrame& d = f.d[i];
             HIPF(hipSetDevice(d.device));
             if (i == 0) {
-              HIPF(hipMemcpyAsync(d.rgb, rgb, n * 12, hipMemcpyHostToDevice, d.st));
-              HIPF(hipMemcpyAsync(d.b, bounces, n * 4, hipMemcpyHostToDevice, d.st));
+              HIPF(hipMemcpyAsync(d.rgb.p, rgb, n * 12, hipMemcpyHostToDevice, d.st));
+              HIPF(hipMemcpyAsync(d.b.p, bounces, n * 4, hipMemcpyHostToDevice, d.st));
               HIPF(hipStreamSynchronize(d.st));
               return;
             }
@@ -432,8 +433,8 @@ int multi_render(MultiDev* m, const mrt_render_args* a, float* rgb, uint32_t* bo
               memcpy(&slab[4 * (size_t)k], rgb + 3 * (size_t)p, 12);
               slab[4 * (size_t)k + 3] = bounces[p];
             }
-            HIPF(hipMemcpyAsync(d.slab, slab.data(), slab.size() * 4, hipMemcpyHostToDevice, d.st));
-            MRTF(d.ctx, mrt_shard_unpack_device(d.ctx, f.W, f.H, f.shard(i), f.shards(), d.slab, d.rgb, d.b, d.st));
+            HIPF(hipMemcpyAsync(d.slab.p, slab.data(), slab.size() * 4, hipMemcpyHostToDevice, d.st));
+            MRTF(d.ctx, mrt_shard_unpack_device(d.ctx, f.W, f.H, f.shard(i), f.shards(), d.slab.p, d.rgb.p, d.b.p, d.st));
             HIPF(hipStreamSynchronize(d.st));  // the host slab goes out of scope
           } catch (const Fail& e) {
             fails[i] = e;
@@ -446,8 +447,8 @@ int multi_render(MultiDev* m, const mrt_render_args* a, float* rgb, uint32_t* bo
     f.render(*a);
     f.gather();
     HIPF(hipSetDevice(f.d[0].device));
-    HIPF(hipMemcpyAsync(rgb, f.d[0].rgb, n * 12, hipMemcpyDeviceToHost, f.d[0].st));
-    HIPF(hipMemcpyAsync(bounces, f.d[0].b, n * 4, hipMemcpyDeviceToHost, f.d[0].st));
+    HIPF(hipMemcpyAsync(rgb, f.d[0].rgb.p, n * 12, hipMemcpyDeviceToHost, f.d[0].st));
+    HIPF(hipMemcpyAsync(bounces, f.d[0].b.p, n * 4, hipMemcpyDeviceToHost, f.d[0].st));
     HIPF(hipStreamSynchronize(f.d[0].st));
     return MRT_OK;
   } catch (const Fail& e) {
@@ -502,10 +503,10 @@ struct mrt_image {
   Frame f;
   uint32_t passes = 0;
   bool gathered = true;  // device 0's buffers hold every device's tiles
-  float* aux = nullptr;  // device 0: albedo then normal (W*H*3 each), zero before a pre-pass
-  uint8_t* rgb8 = nullptr;  // device 0: display bytes
-  mrt_denoise_params dn{};   // the Denoise view's filter (mrt_image_set_denoise)
-  float* dn_rgb = nullptr;   // device 0: the filtered colour (W*H*3)
+  DevBuf<float> aux;     // device 0: albedo then normal (W*H*3 each), none before a pre-pass
+  DevBuf<uint8_t> rgb8;  // device 0: display bytes
+  mrt_denoise_params dn{};  // the Denoise view's filter (mrt_image_set_denoise)
+  DevBuf<float> dn_rgb;  // device 0: the filtered colour (W*H*3)
 };
 
 extern "C" {
@@ -619,9 +620,7 @@ int mrt_image_destroy(mrt_image* img) {
   if (!img->f.d.empty()) {
     hipSetDevice(img->f.d[0].device);
     if (img->f.d[0].st) hipStreamSynchronize(img->f.d[0].st);
-    hipFree(img->aux);
-    hipFree(img->rgb8);
-    hipFree(img->dn_rgb);
+    (void)img->aux.free(), (void)img->rgb8.free(), (void)img->dn_rgb.free();
   }
   ctx_images(img->ctx, -1);
   delete img;
@@ -659,8 +658,8 @@ int mrt_image_prepass(mrt_image* img, uint64_t seed) {
     DevFrame& d0 = img->f.d[0];
     const size_t n = img->f.npix();
     HIPF(hipSetDevice(d0.device));
-    if (!img->aux) HIPF(hipMalloc(&img->aux, n * 24));
-    MRTF(d0.ctx, mrt_prepass_device(d0.ctx, img->f.W, img->f.H, seed, img->aux, img->aux + 3 * n, d0.st));
+    HIPF(img->aux.reserve(n * 6));
+    MRTF(d0.ctx, mrt_prepass_device(d0.ctx, img->f.W, img->f.H, seed, img->aux.p, img->aux.p + 3 * n, d0.st));
   });
 }
 
@@ -678,8 +677,8 @@ int mrt_image_read(mrt_image* img, float* rgb, uint32_t* bounces, uint32_t* pass
     DevFrame& d0 = img->f.d[0];
     const size_t n = img->f.npix();
     HIPF(hipSetDevice(d0.device));
-    if (rgb) HIPF(hipMemcpyAsync(rgb, d0.rgb, n * 12, hipMemcpyDeviceToHost, d0.st));
-    if (bounces) HIPF(hipMemcpyAsync(bounces, d0.b, n * 4, hipMemcpyDeviceToHost, d0.st));
+    if (rgb) HIPF(hipMemcpyAsync(rgb, d0.rgb.p, n * 12, hipMemcpyDeviceToHost, d0.st));
+    if (bounces) HIPF(hipMemcpyAsync(bounces, d0.b.p, n * 4, hipMemcpyDeviceToHost, d0.st));
     HIPF(hipStreamSynchronize(d0.st));
     if (passes) *passes = img->passes;
   });
@@ -712,21 +711,21 @@ int mrt_image_tonemap(mrt_image* img, uint32_t mode, uint8_t* out) {
       img->gathered = true;
     }
     HIPF(hipSetDevice(d0.device));
-    if (!img->rgb8) HIPF(hipMalloc(&img->rgb8, n * 3));
-    if (aux && !img->aux) {  // Image::to_rgb_bytes: no buffer yet -> zeros
-      HIPF(hipMemsetAsync(img->rgb8, 0, n * 3, d0.st));
+    HIPF(img->rgb8.reserve(n * 3));
+    if (aux && !img->aux.p) {  // Image::to_rgb_bytes: no buffer yet -> zeros
+      HIPF(hipMemsetAsync(img->rgb8.p, 0, n * 3, d0.st));
     } else if (mode == MRT_DISPLAY_DENOISE) {  // main.rs:675-683: filter, then Default's bytes
-      if (!img->dn_rgb) HIPF(hipMalloc(&img->dn_rgb, n * 12));
-      const float* albedo = img->aux;  // colour-only before a pre-pass (main.rs:737-743)
-      MRTF(d0.ctx, mrt_denoise_device(d0.ctx, img->f.W, img->f.H, d0.rgb, img->passes, albedo,
-                                      albedo ? albedo + 3 * n : nullptr, &img->dn, img->dn_rgb, d0.st));
-      MRTF(d0.ctx, mrt_tonemap_device(d0.ctx, img->f.W, img->f.H, img->dn_rgb, d0.b, img->passes ? 1 : 0,
-                                      MRT_DISPLAY_DEFAULT, img->rgb8, d0.st));
+      HIPF(img->dn_rgb.reserve(n * 3));
+      const float* albedo = img->aux.p;  // colour-only before a pre-pass (main.rs:737-743)
+      MRTF(d0.ctx, mrt_denoise_device(d0.ctx, img->f.W, img->f.H, d0.rgb.p, img->passes, albedo,
+                                      albedo ? albedo + 3 * n : nullptr, &img->dn, img->dn_rgb.p, d0.st));
+      MRTF(d0.ctx, mrt_tonemap_device(d0.ctx, img->f.W, img->f.H, img->dn_rgb.p, d0.b.p, img->passes ? 1 : 0,
+                                      MRT_DISPLAY_DEFAULT, img->rgb8.p, d0.st));
     } else {
-      const float* src = aux ? img->aux + (mode == MRT_DISPLAY_NORMAL ? 3 * n : 0) : d0.rgb;
-      MRTF(d0.ctx, mrt_tonemap_device(d0.ctx, img->f.W, img->f.H, src, d0.b, img->passes, mode, img->rgb8, d0.st));
+      const float* src = aux ? img->aux.p + (mode == MRT_DISPLAY_NORMAL ? 3 * n : 0) : d0.rgb.p;
+      MRTF(d0.ctx, mrt_tonemap_device(d0.ctx, img->f.W, img->f.H, src, d0.b.p, img->passes, mode, img->rgb8.p, d0.st));
     }
-    HIPF(hipMemcpyAsync(out, img->rgb8, n * 3, hipMemcpyDeviceToHost, d0.st));
+    HIPF(hipMemcpyAsync(out, img->rgb8.p, n * 3, hipMemcpyDeviceToHost, d0.st));
     HIPF(hipStreamSynchronize(d0.st));
   });
 }

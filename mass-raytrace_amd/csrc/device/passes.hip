@@ -304,7 +304,7 @@ __global__ __launch_bounds__(kBlock) void k_selftest_slab(unsigned long long n, 
 int shard_exchange(mrt_ctx* c, uint32_t W, uint32_t H, uint32_t si, uint32_t sc, const void* src_rgb,
                    const void* src_b, const void* slab, float* dst_rgb, uint32_t* dst_b, void* stream, bool pack) {
   return guarded(c, [&] {
-    if (W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 32)) throw ApiError{MRT_ERR_INVALID, "bad image size"};
+    check_image_size(W, H);
     if (sc == 0) sc = 1;
     if (si >= sc) throw ApiError{MRT_ERR_INVALID, "shard_index >= shard_count"};
     if (!slab || (pack && (!src_rgb || !src_b)) || (!pack && (!dst_rgb || !dst_b)))
@@ -323,6 +323,19 @@ int shard_exchange(mrt_ctx* c, uint32_t W, uint32_t H, uint32_t si, uint32_t sc,
   });
 }
 
+// A selftest kernel's N counters: zeroed, the kernel run over (n, seed), read back.
+template <size_t N, typename K>
+void run_selftest(mrt_ctx* c, K kernel, uint64_t n, uint64_t seed, unsigned long long (&h)[N]) {
+  DevBuf<unsigned long long> d;
+  HIP_CHECK(d.alloc(N));
+  HIP_CHECK(hipMemsetAsync(d.p, 0, N * 8, c->stream));
+  hipLaunchKernelGGL(kernel, dim3(4096), dim3(kBlock), 0, c->stream, (unsigned long long)n, (unsigned long long)seed,
+                     d.p);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(h, d.p, N * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_CHECK(hipStreamSynchronize(c->stream));
+}
+
 }  // namespace
 
 extern "C" {
@@ -331,17 +344,9 @@ int mrt_selftest_division(mrt_ctx* c, uint64_t n, uint64_t seed, uint64_t* misma
   MRT_DEV0(c, mrt_selftest_division(c, n, seed, mismatches));
   return guarded(c, [&] {
     if (!mismatches) throw ApiError{MRT_ERR_INVALID, "null output"};
-    unsigned long long* d = nullptr;
-    HIP_CHECK(hipMalloc(&d, 8));
-    HIP_CHECK(hipMemsetAsync(d, 0, 8, c->stream));
-    hipLaunchKernelGGL(k_selftest_division, dim3(4096), dim3(kBlock), 0, c->stream, (unsigned long long)n,
-                       (unsigned long long)seed, d);
-    HIP_CHECK(hipGetLastError());
-    unsigned long long h = 0;
-    HIP_CHECK(hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    HIP_CHECK(hipFree(d));
-    *mismatches = h;
+    unsigned long long h[1];
+    run_selftest(c, k_selftest_division, n, seed, h);
+    *mismatches = h[0];
   });
 }
 
@@ -349,7 +354,7 @@ int mrt_tonemap_device(mrt_ctx* c, uint32_t W, uint32_t H, const float* d_rgb, c
                        uint32_t mode, uint8_t* d_out, void* stream) {
   MRT_DEV0(c, mrt_tonemap_device(c, W, H, d_rgb, d_b, passes, mode, d_out, stream));
   return guarded(c, [&] {
-    if (W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 32)) throw ApiError{MRT_ERR_INVALID, "bad image size"};
+    check_image_size(W, H);
     if (mode > MRT_DISPLAY_NORMAL) throw ApiError{MRT_ERR_INVALID, "bad display mode"};
     const bool aux = mode == MRT_DISPLAY_ALBEDO || mode == MRT_DISPLAY_NORMAL;
     if (!d_out || (aux && !d_rgb) ||
@@ -357,18 +362,19 @@ int mrt_tonemap_device(mrt_ctx* c, uint32_t W, uint32_t H, const float* d_rgb, c
       throw ApiError{MRT_ERR_INVALID, "null buffer"};
     hipStream_t st = (hipStream_t)stream;  // NULL: the null stream (ordered with the caller's default-stream work)
     const uint32_t n = W * H;
-    if (!c->gamma_d) {
-      HIP_CHECK(hipMalloc(&c->gamma_d, 256 * 4));
-      HIP_CHECK(hipMemcpy(c->gamma_d, mrt::gamma_thresholds().data(), 256 * 4, hipMemcpyHostToDevice));
+    if (!c->gamma_d.p) {
+      HIP_CHECK(c->gamma_d.alloc(256));
+      HIP_CHECK(hipMemcpy(c->gamma_d.p, mrt::gamma_thresholds().data(), 256 * 4, hipMemcpyHostToDevice));
     }
-    HIP_CHECK(hipMemsetAsync(c->work + 1, 0, 4, st));  // word 1 of the work line: max count
+    uint32_t* d_max = c->work.p + 1;  // word 1 of the work line: max count
+    HIP_CHECK(hipMemsetAsync(d_max, 0, 4, st));
     if (mode == MRT_DISPLAY_DEPTH && passes) {
       hipLaunchKernelGGL(k_max_u32, dim3(std::min<uint32_t>((n + kBlock - 1) / kBlock, 4096u)), dim3(kBlock), 0, st,
-                         d_b, n, c->work + 1);
+                         d_b, n, d_max);
       HIP_CHECK(hipGetLastError());
     }
     hipLaunchKernelGGL(k_tonemap, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, W, H, d_rgb, d_b, passes,
-                       mode, (const uint32_t*)(c->work + 1), (const uint32_t*)c->gamma_d, d_out);
+                       mode, (const uint32_t*)d_max, (const uint32_t*)c->gamma_d.p, d_out);
     HIP_CHECK(hipGetLastError());
   });
 }
@@ -377,24 +383,20 @@ int mrt_tonemap(mrt_ctx* c, uint32_t W, uint32_t H, const float* rgb, const uint
                 uint32_t mode, uint8_t* out) {
   MRT_DEV0(c, mrt_tonemap(c, W, H, rgb, b, passes, mode, out));
   return guarded(c, [&] {
-    if (W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 32)) throw ApiError{MRT_ERR_INVALID, "bad image size"};
+    check_image_size(W, H);
     if (!out || !rgb || !b) throw ApiError{MRT_ERR_INVALID, "null buffer"};
     const size_t n = (size_t)W * H;
-    void* mem = nullptr;
-    HIP_CHECK(hipMalloc(&mem, n * 12 + n * 4 + n * 3 + 256));
-    float* d_rgb = (float*)mem;
+    DevBuf<char> mem;
+    HIP_CHECK(mem.alloc(n * 12 + n * 4 + n * 3 + 256));
+    float* d_rgb = (float*)mem.p;
     uint32_t* d_b = (uint32_t*)(d_rgb + 3 * n);
     uint8_t* d_out = (uint8_t*)(d_b + n);
     HIP_CHECK(hipMemcpyAsync(d_rgb, rgb, n * 12, hipMemcpyHostToDevice, c->stream));
     HIP_CHECK(hipMemcpyAsync(d_b, b, n * 4, hipMemcpyHostToDevice, c->stream));
-    int rc = mrt_tonemap_device(c, W, H, d_rgb, d_b, passes, mode, d_out, c->stream);
-    if (rc != MRT_OK) {
-      hipFree(mem);
-      throw ApiError{rc, c->err};
-    }
+    const int rc = mrt_tonemap_device(c, W, H, d_rgb, d_b, passes, mode, d_out, c->stream);
+    if (rc != MRT_OK) throw ApiError{rc, c->err};
     HIP_CHECK(hipMemcpyAsync(out, d_out, n * 3, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipStreamSynchronize(c->stream));
-    HIP_CHECK(hipFree(mem));
   });
 }
 
@@ -404,14 +406,15 @@ int mrt_prepass_device(mrt_ctx* c, uint32_t W, uint32_t H, uint64_t seed, float*
   return guarded(c, [&] {
     if (!c->has_scene) throw ApiError{MRT_ERR_STATE, "no scene uploaded"};
     if (!c->has_camera) throw ApiError{MRT_ERR_STATE, "no camera set"};
-    if (W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 32)) throw ApiError{MRT_ERR_INVALID, "bad image size"};
+    check_image_size(W, H);
     if (!d_albedo || !d_normal) throw ApiError{MRT_ERR_INVALID, "null buffer"};
     hipStream_t st = (hipStream_t)stream;  // NULL: the null stream (ordered with the caller's default-stream work)
     wait_queues(c, st);
     const uint32_t n = W * H;
     ensure_slots(c, n);  // the pre-pass rays
-    auto* prepass = c->facts.trav_rng ? (c->scene_ext ? k_prepass<true, true> : k_prepass<true, false>)
-                                      : (c->scene_ext ? k_prepass<false, true> : k_prepass<false, false>);
+    auto* prepass = with_value<true, false>(c->facts.trav_rng, [&](auto RNG) {
+      return with_value<true, false>(c->scene_ext, [&](auto EXT) { return &k_prepass<RNG, EXT>; });
+    });
     hipLaunchKernelGGL(prepass, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, c->S, c->cam, W, H,
                        (unsigned long long)seed, c->slot_ro, c->slot_rd, d_albedo, d_normal);
     HIP_CHECK(hipGetLastError());
@@ -422,20 +425,16 @@ int mrt_prepass_device(mrt_ctx* c, uint32_t W, uint32_t H, uint64_t seed, float*
 int mrt_prepass(mrt_ctx* c, uint32_t W, uint32_t H, uint64_t seed, float* albedo, float* normal) {
   MRT_DEV0(c, mrt_prepass(c, W, H, seed, albedo, normal));
   return guarded(c, [&] {
-    if (W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 32)) throw ApiError{MRT_ERR_INVALID, "bad image size"};
+    check_image_size(W, H);
     if (!albedo || !normal) throw ApiError{MRT_ERR_INVALID, "null buffer"};
     const size_t n = (size_t)W * H;
-    float* d = nullptr;
-    HIP_CHECK(hipMalloc(&d, n * 24));
-    int rc = mrt_prepass_device(c, W, H, seed, d, d + 3 * n, c->stream);
-    if (rc != MRT_OK) {
-      hipFree(d);
-      throw ApiError{rc, c->err};
-    }
-    HIP_CHECK(hipMemcpyAsync(albedo, d, n * 12, hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipMemcpyAsync(normal, d + 3 * n, n * 12, hipMemcpyDeviceToHost, c->stream));
+    DevBuf<float> d;
+    HIP_CHECK(d.alloc(n * 6));
+    const int rc = mrt_prepass_device(c, W, H, seed, d.p, d.p + 3 * n, c->stream);
+    if (rc != MRT_OK) throw ApiError{rc, c->err};
+    HIP_CHECK(hipMemcpyAsync(albedo, d.p, n * 12, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipMemcpyAsync(normal, d.p + 3 * n, n * 12, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipStreamSynchronize(c->stream));
-    HIP_CHECK(hipFree(d));
   });
 }
 
@@ -448,25 +447,20 @@ int mrt_shade_rays(mrt_ctx* c, const float* rays, uint32_t n, float t_min, float
     if (!rays || !out) throw ApiError{MRT_ERR_INVALID, "null argument"};
     wait_queues(c, c->stream);
     ensure_slots(c, n);  // the rays where the traversal re-reads them
-    char* mem = nullptr;
+    DevBuf<char> mem;
     const size_t ray_bytes = ((size_t)n * 24 + 255) & ~(size_t)255;
-    HIP_CHECK(hipMalloc(&mem, ray_bytes + (size_t)n * sizeof(mrt_shade_out)));
-    float* d_rays = (float*)mem;
-    mrt_shade_out* d_out = (mrt_shade_out*)(mem + ray_bytes);
-    try {
-      HIP_CHECK(hipMemcpyAsync(d_rays, rays, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
-      auto* f = c->facts.trav_rng ? (c->scene_ext ? k_shade_rays<true, true> : k_shade_rays<true, false>)
-                                  : (c->scene_ext ? k_shade_rays<false, true> : k_shade_rays<false, false>);
-      hipLaunchKernelGGL(f, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->S, (const float*)d_rays, n,
-                         t_min, t_max, (unsigned long long)seed, c->slot_ro, c->slot_rd, d_out);
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(mrt_shade_out), hipMemcpyDeviceToHost, c->stream));
-      HIP_CHECK(hipStreamSynchronize(c->stream));
-    } catch (...) {
-      hipFree(mem);
-      throw;
-    }
-    HIP_CHECK(hipFree(mem));
+    HIP_CHECK(mem.alloc(ray_bytes + (size_t)n * sizeof(mrt_shade_out)));
+    float* d_rays = (float*)mem.p;
+    mrt_shade_out* d_out = (mrt_shade_out*)(mem.p + ray_bytes);
+    HIP_CHECK(hipMemcpyAsync(d_rays, rays, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
+    auto* f = with_value<true, false>(c->facts.trav_rng, [&](auto RNG) {
+      return with_value<true, false>(c->scene_ext, [&](auto EXT) { return &k_shade_rays<RNG, EXT>; });
+    });
+    hipLaunchKernelGGL(f, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->S, (const float*)d_rays, n,
+                       t_min, t_max, (unsigned long long)seed, c->slot_ro, c->slot_rd, d_out);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(mrt_shade_out), hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
     mark_ctx_busy(c, c->stream);  // slot_ro/slot_rd are shared with the drain hand-off
   });
 }
@@ -475,16 +469,8 @@ int mrt_selftest_slab(mrt_ctx* c, uint64_t n, uint64_t seed, uint64_t* mismatche
   MRT_DEV0(c, mrt_selftest_slab(c, n, seed, mismatches, near_ties));
   return guarded(c, [&] {
     if (!mismatches || !near_ties) throw ApiError{MRT_ERR_INVALID, "null output"};
-    unsigned long long* d = nullptr;
-    HIP_CHECK(hipMalloc(&d, 16));
-    HIP_CHECK(hipMemsetAsync(d, 0, 16, c->stream));
-    hipLaunchKernelGGL(k_selftest_slab, dim3(4096), dim3(kBlock), 0, c->stream, (unsigned long long)n,
-                       (unsigned long long)seed, d);
-    HIP_CHECK(hipGetLastError());
-    unsigned long long h[2] = {0, 0};
-    HIP_CHECK(hipMemcpyAsync(h, d, 16, hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
-    HIP_CHECK(hipFree(d));
+    unsigned long long h[2];
+    run_selftest(c, k_selftest_slab, n, seed, h);
     *mismatches = h[0];
     *near_ties = h[1];
   });

@@ -408,13 +408,11 @@ std::mutex g_alloc_mutex;
 void plan_buffers(mrt_ctx* c, uint32_t n_pix, uint32_t& spp_chunk, bool need_pool) {
   std::lock_guard<std::mutex> lock(g_alloc_mutex);
   if (pool_wanted(n_pix, spp_chunk, c->tun.pool_paths, need_pool) <= c->pool_cap &&
-      (size_t)n_pix * spp_chunk <= c->results_cap)
+      (size_t)n_pix * spp_chunk <= c->results.n)
     return;
   HIP_CHECK(hipDeviceSynchronize());  // the queues may still use the old buffers
   release_pool(c);
-  if (c->results) HIP_CHECK(hipFree(c->results));
-  c->results = nullptr;
-  c->results_cap = 0;
+  HIP_CHECK(c->results.free());
   size_t free_b = 0, total_b = 0;
   HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
   const size_t reserve = c->tun.mem_reserve;
@@ -425,8 +423,7 @@ void plan_buffers(mrt_ctx* c, uint32_t n_pix, uint32_t& spp_chunk, bool need_poo
                                       std::to_string(reserve >> 20) + ": not even one sample per pixel fits"};
   spp_chunk = plan.spp_chunk;
   if (plan.P) ensure_pool(c, plan.P);
-  HIP_CHECK(hipMalloc(&c->results, (size_t)n_pix * spp_chunk * 16));  // released above
-  c->results_cap = (size_t)n_pix * spp_chunk;
+  HIP_CHECK(c->results.alloc((size_t)n_pix * spp_chunk));
 }
 
 // One chunk's parameters: `cs` samples per pixel from sample `done` of the
@@ -452,9 +449,9 @@ void launch_finish(mrt_ctx* c, int qi, uint32_t cur, const RenderParams& rp, boo
   ensure_slots(c, lanes * kMaxQueues);
   float4* sro = c->slot_ro + lanes * qi;
   float4* srd = c->slot_rd + lanes * qi;
-  HIP_CHECK(hipMemsetAsync(&q.ctrl->next_work, 0, 4, q.stream));
+  HIP_CHECK(hipMemsetAsync(&q.ctrl.p->next_work, 0, 4, q.stream));
   hipLaunchKernelGGL(render_kernel(count, c->scene_alpha, true), dim3(grid), dim3(kBlock), 0, q.stream, c->S, c->cam, rp,
-                     sro, srd, q.ctrl, res, c->d_cnt, c->tun.trace, q.bufs[cur], cur);
+                     sro, srd, q.ctrl.p, res, c->d_cnt.p, c->tun.trace, q.bufs[cur], cur);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -462,7 +459,7 @@ void launch_finish(mrt_ctx* c, int qi, uint32_t cur, const RenderParams& rp, boo
 // (k_accumulate: in sample order).
 void accumulate(mrt_ctx* c, const RenderParams& rp, float* d_rgb, uint32_t* d_b, hipStream_t st) {
   hipLaunchKernelGGL(k_accumulate, dim3((rp.n_pix + kAccPix - 1) / kAccPix), dim3(kBlock), 0, st,
-                     (const float4*)c->results, rp.n_pix, rp.spp, rp.pixlist, d_rgb, d_b);
+                     (const float4*)c->results.p, rp.n_pix, rp.spp, rp.pixlist, d_rgb, d_b);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -478,13 +475,13 @@ void render_fused(mrt_ctx* c, const mrt_render_args* a, const uint32_t* pixlist_
     if (a->max_depth == 0) continue;  // trace(ray, 0) returns (0, 0): nothing to add
     const RenderParams rp = chunk_params(c, a, pixlist_d, n_pix, done, cs, 0);
     const Ctrl init = ctrl_init(0);
-    HIP_CHECK(hipMemcpyAsync(c->q[0].ctrl, &init, sizeof(Ctrl), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(c->q[0].ctrl.p, &init, sizeof(Ctrl), hipMemcpyHostToDevice, st));
     if (timing) HIP_CHECK(hipEventRecord(c->tev[0], st));
     const RenderFn f = render_kernel(count, c->scene_alpha, false);
     const uint32_t grid = persistent_grid(c, (const void*)f, 0);
     ensure_slots(c, (size_t)grid * kBlock);
-    hipLaunchKernelGGL(f, dim3(grid), dim3(kBlock), 0, st, c->S, c->cam, rp, c->slot_ro, c->slot_rd, c->q[0].ctrl,
-                       c->results, c->d_cnt, c->tun.trace, PathBufs{}, 0u);
+    hipLaunchKernelGGL(f, dim3(grid), dim3(kBlock), 0, st, c->S, c->cam, rp, c->slot_ro, c->slot_rd, c->q[0].ctrl.p,
+                       c->results.p, c->d_cnt.p, c->tun.trace, PathBufs{}, 0u);
     HIP_CHECK(hipGetLastError());
     if (timing) {
       HIP_CHECK(hipEventRecord(c->tev[1], st));
@@ -513,8 +510,7 @@ void wait_queues(mrt_ctx* c, hipStream_t st) {
 }
 
 void release_pool(mrt_ctx* c) {
-  if (c->pool_mem) HIP_CHECK(hipFree(c->pool_mem));
-  c->pool_mem = nullptr;
+  HIP_CHECK(c->pool.free());
   c->pool_cap = 0;
 }
 
@@ -525,8 +521,8 @@ void ensure_pool(mrt_ctx* c, size_t P) {
   release_pool(c);
   const int K = c->tun.queues;
   const size_t per_q = (P + K - 1) / K;
-  HIP_CHECK(hipMalloc(&c->pool_mem, pool_bytes(K, P)));
-  char* p = (char*)c->pool_mem;
+  HIP_CHECK(c->pool.alloc(pool_bytes(K, P)));
+  char* p = c->pool.p;
   auto take = [&](size_t bytes) {
     char* r = p;
     p += (bytes + 255) & ~(size_t)255;
@@ -548,14 +544,12 @@ void ensure_pool(mrt_ctx* c, size_t P) {
 }
 
 void ensure_slots(mrt_ctx* c, size_t n) {
-  if (n <= c->slots_cap) return;
-  if (c->slot_ro) HIP_CHECK(hipDeviceSynchronize());  // a queue set's drain may still use them
-  if (c->slot_ro) HIP_CHECK(hipFree(c->slot_ro));
-  c->slot_ro = nullptr;
-  c->slot_rd = nullptr;
-  HIP_CHECK(hipMalloc(&c->slot_ro, 32 * n));
-  c->slot_rd = c->slot_ro + n;
-  c->slots_cap = n;
+  if (2 * n <= c->slots.n) return;
+  if (c->slots.p) HIP_CHECK(hipDeviceSynchronize());  // a queue set's drain may still use them
+  c->slot_ro = c->slot_rd = nullptr;
+  HIP_CHECK(c->slots.alloc(2 * n));
+  c->slot_ro = c->slots.p;
+  c->slot_rd = c->slots.p + n;
 }
 
 // MRT_TILE x MRT_TILE tiles in raster order; shard si of sc owns t % sc == si;
@@ -577,16 +571,14 @@ std::vector<uint32_t> shard_pixel_list(uint32_t W, uint32_t H, uint32_t si, uint
 std::pair<uint32_t*, uint32_t> pixlist(mrt_ctx* c, uint32_t W, uint32_t H, uint32_t si, uint32_t sc) {
   auto key = std::make_tuple(W, H, si, sc);
   auto it = c->pixlists.find(key);
-  if (it != c->pixlists.end()) return it->second;
-  const std::vector<uint32_t> list = shard_pixel_list(W, H, si, sc);
-  uint32_t* d = nullptr;
-  if (!list.empty()) {
-    HIP_CHECK(hipMalloc(&d, list.size() * 4));
-    HIP_CHECK(hipMemcpy(d, list.data(), list.size() * 4, hipMemcpyHostToDevice));
+  if (it == c->pixlists.end()) {
+    const std::vector<uint32_t> list = shard_pixel_list(W, H, si, sc);
+    DevBuf<uint32_t> d;
+    HIP_CHECK(d.alloc(list.size()));
+    if (d.p) HIP_CHECK(hipMemcpy(d.p, list.data(), list.size() * 4, hipMemcpyHostToDevice));
+    it = c->pixlists.emplace(key, std::move(d)).first;
   }
-  auto v = std::make_pair(d, (uint32_t)list.size());
-  c->pixlists[key] = v;
-  return v;
+  return {it->second.p, (uint32_t)it->second.n};
 }
 
 // Work enqueued on a caller's stream `st` that writes the context's shared
@@ -665,7 +657,7 @@ void fork_queues(mrt_ctx* c, const RenderParams& rp) {
   const int K = c->tun.queues;
   const uint32_t n0 = (uint32_t)std::min<size_t>(rp.G, c->pool_cap);
   HIP_CHECK(hipStreamWaitEvent(c->q[0].stream, c->acc_done, 0));
-  HIP_CHECK(hipMemcpyAsync(c->work, &n0, 4, hipMemcpyHostToDevice, c->q[0].stream));
+  HIP_CHECK(hipMemcpyAsync(c->work.p, &n0, 4, hipMemcpyHostToDevice, c->q[0].stream));
   HIP_CHECK(hipEventRecord(c->set_fork, c->q[0].stream));
   uint32_t base = 0;
   for (int k = 0; k < K; ++k) {
@@ -673,7 +665,7 @@ void fork_queues(mrt_ctx* c, const RenderParams& rp) {
     const uint32_t nk = queue_share(n0, K, k);  // <= q.cap
     if (k) HIP_CHECK(hipStreamWaitEvent(q.stream, c->set_fork, 0));
     const Ctrl init = ctrl_init(nk);
-    HIP_CHECK(hipMemcpyAsync(q.ctrl, &init, sizeof(Ctrl), hipMemcpyHostToDevice, q.stream));
+    HIP_CHECK(hipMemcpyAsync(q.ctrl.p, &init, sizeof(Ctrl), hipMemcpyHostToDevice, q.stream));
     if (nk) {
       hipLaunchKernelGGL(k_generate, dim3((nk + kBlock - 1) / kBlock), dim3(kBlock), 0, q.stream, c->cam, rp,
                          q.bufs[0], base, nk);
@@ -695,18 +687,18 @@ void enqueue_batch(mrt_ctx* c, Queue& q, QueueLoop& L, const RenderParams& rp, c
       launch_trace(c, q.stream, q, q.bufs[cur], cur, p.count, kTmin, INFINITY);
     const hipEvent_t m1 = t.stamp(q.stream);
     hipLaunchKernelGGL(p.shade, dim3(shade_workgroups(q.cap, L.bound, kShadeBlock)), dim3(kShadeBlock), 0, q.stream,
-                       c->S, rp, q.bufs[cur], q.bufs[cur ^ 1], (const uint4*)q.hits, q.ctrl, cur, c->results, c->d_cnt);
+                       c->S, rp, q.bufs[cur], q.bufs[cur ^ 1], (const uint4*)q.hits, q.ctrl.p, cur, c->results.p, c->d_cnt.p);
     HIP_CHECK(hipGetLastError());
     if (!L.exhausted || rp.shade_bin == 2) {  // new paths behind the survivors (shade_bin 2: and the pool's ends joined)
-      hipLaunchKernelGGL(k_reserve, dim3(1), dim3(64), 0, q.stream, q.ctrl, cur, c->work, rp.G, rp.pool_cap);
+      hipLaunchKernelGGL(k_reserve, dim3(1), dim3(64), 0, q.stream, q.ctrl.p, cur, c->work.p, rp.G, rp.pool_cap);
       hipLaunchKernelGGL(k_refill, dim3(c->refill_grid), dim3(kBlock), 0, q.stream, c->cam, rp, q.bufs[cur ^ 1],
-                         (const Ctrl*)q.ctrl);
+                         (const Ctrl*)q.ctrl.p);
       HIP_CHECK(hipGetLastError());
     }
     const hipEvent_t m2 = t.stamp(q.stream);
     if (t.timing) t.marks.push_back({m0, m1, m2});
   }
-  hipLaunchKernelGGL(k_status, dim3(1), dim3(64), 0, q.stream, (const Ctrl*)q.ctrl, (const uint32_t*)c->work,
+  hipLaunchKernelGGL(k_status, dim3(1), dim3(64), 0, q.stream, (const Ctrl*)q.ctrl.p, (const uint32_t*)c->work.p,
                      q.d_stat + L.slot);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipEventRecord(q.ev[L.slot], q.stream));
@@ -733,7 +725,7 @@ bool read_status(mrt_ctx* c, int k, QueueLoop& L, const RenderParams& rp, const 
     fail_chunk(c, "internal: a k_shade grid was smaller than its live pool (" + std::to_string(s.shade_short) + " paths)");
   if (step == LoopStep::kHandOff) {
     const hipEvent_t f0 = t.stamp(q.stream);
-    launch_finish(c, k, L.it & 1, rp, p.count, c->results);
+    launch_finish(c, k, L.it & 1, rp, p.count, c->results.p);
     const hipEvent_t f1 = t.stamp(q.stream);
     if (t.timing) t.fin.push_back({f0, f1});
   }
@@ -848,20 +840,15 @@ int mrt_render(mrt_ctx* c, const mrt_render_args* a, float* rgb, uint32_t* bounc
   return guarded(c, [&] {
     if (!a || !rgb || !bounces) throw ApiError{MRT_ERR_INVALID, "null argument"};
     size_t np = (size_t)a->width * a->height;
-    if (np > c->acc_cap) {
-      hipFree(c->d_acc_rgb);
-      hipFree(c->d_acc_b);
-      c->d_acc_rgb = nullptr;
-      c->d_acc_b = nullptr;
-      HIP_CHECK(hipMalloc(&c->d_acc_rgb, np * 12));
-      HIP_CHECK(hipMalloc(&c->d_acc_b, np * 4));
-      c->acc_cap = np;
-    }
-    HIP_CHECK(hipMemcpyAsync(c->d_acc_rgb, rgb, np * 12, hipMemcpyHostToDevice, c->stream));
-    HIP_CHECK(hipMemcpyAsync(c->d_acc_b, bounces, np * 4, hipMemcpyHostToDevice, c->stream));
-    render_device(c, a, c->d_acc_rgb, c->d_acc_b, c->stream);
-    HIP_CHECK(hipMemcpyAsync(rgb, c->d_acc_rgb, np * 12, hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipMemcpyAsync(bounces, c->d_acc_b, np * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(c->d_acc_rgb.reserve(np * 3));
+    HIP_CHECK(c->d_acc_b.reserve(np));
+    float* d_rgb = c->d_acc_rgb.p;
+    uint32_t* d_b = c->d_acc_b.p;
+    HIP_CHECK(hipMemcpyAsync(d_rgb, rgb, np * 12, hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(hipMemcpyAsync(d_b, bounces, np * 4, hipMemcpyHostToDevice, c->stream));
+    render_device(c, a, d_rgb, d_b, c->stream);
+    HIP_CHECK(hipMemcpyAsync(rgb, d_rgb, np * 12, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipMemcpyAsync(bounces, d_b, np * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipStreamSynchronize(c->stream));
   });
 }

@@ -333,13 +333,13 @@ void launch_trace(mrt_ctx* c, hipStream_t st, const Queue& q, const PathBufs& in
     smem = lds ? (size_t)c->S.n_tlet * 16 : (size_t)kStashQuads * block * 16;  // the treelet, or the world-ray stash (4 x 16 B per lane)
     grid = persistent_grid(c, (const void*)f, smem, shared, block, 3, 4);
   }
-  hipLaunchKernelGGL(f, dim3(grid), dim3(block), smem, st, c->S, in, q.hits, q.ctrl, cur, c->d_cnt, tmin, tmax, t.trace);
+  hipLaunchKernelGGL(f, dim3(grid), dim3(block), smem, st, c->S, in, q.hits, q.ctrl.p, cur, c->d_cnt.p, tmin, tmax, t.trace);
   HIP_CHECK(hipGetLastError());
 }
 
 void launch_trace_simple(mrt_ctx* c, const Queue& q, uint32_t cur) {
   auto* f = c->facts.trav_rng ? k_trace_simple<true> : k_trace_simple<false>;
-  hipLaunchKernelGGL(f, dim3(c->trace_grid), dim3(kBlock), 0, q.stream, c->S, q.bufs[cur], q.hits, q.ctrl, cur, c->d_cnt);
+  hipLaunchKernelGGL(f, dim3(c->trace_grid), dim3(kBlock), 0, q.stream, c->S, q.bufs[cur], q.hits, q.ctrl.p, cur, c->d_cnt.p);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -349,30 +349,23 @@ extern "C" int mrt_trace_rays(mrt_ctx* c, const float* rays, uint32_t n, float t
     if (!c->has_scene) throw ApiError{MRT_ERR_STATE, "no scene uploaded"};
     if (n == 0) return;
     if (!rays || !out) throw ApiError{MRT_ERR_INVALID, "null argument"};
-    if (n > c->rays_cap) {
-      hipFree(c->d_rays);
-      hipFree(c->d_rhits);
-      c->d_rays = nullptr;
-      c->d_rhits = nullptr;
-      HIP_CHECK(hipMalloc(&c->d_rays, (size_t)n * 24));
-      HIP_CHECK(hipMalloc(&c->d_rhits, (size_t)n * 16));
-      c->rays_cap = n;
-    }
-    HIP_CHECK(hipMemcpyAsync(c->d_rays, rays, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(c->d_rays.reserve((size_t)n * 6));
+    HIP_CHECK(c->d_rhits.reserve(n));
+    HIP_CHECK(hipMemcpyAsync(c->d_rays.p, rays, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
     wait_queues(c, c->stream);
     ensure_pool(c, (size_t)n * c->tun.queues);  // all rays go to queue 0
     const Queue& q = c->q[0];
     const uint32_t g = (n + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_rays_in, dim3(g), dim3(kBlock), 0, c->stream, (const float*)c->d_rays, n, q.bufs[0]);
+    hipLaunchKernelGGL(k_rays_in, dim3(g), dim3(kBlock), 0, c->stream, (const float*)c->d_rays.p, n, q.bufs[0]);
     HIP_CHECK(hipGetLastError());
     const Ctrl init = ctrl_init(n, /*next_work*/ n);
-    HIP_CHECK(hipMemcpyAsync(q.ctrl, &init, sizeof(Ctrl), hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(hipMemcpyAsync(q.ctrl.p, &init, sizeof(Ctrl), hipMemcpyHostToDevice, c->stream));
     launch_trace(c, c->stream, q, q.bufs[0], 0u, true, t_min, t_max);
     hipLaunchKernelGGL(c->scene_ext ? k_rays_out<true> : k_rays_out<false>, dim3(g), dim3(kBlock), 0, c->stream, c->S,
-                       q.bufs[0], (const uint4*)q.hits, n, c->d_rhits);
+                       q.bufs[0], (const uint4*)q.hits, n, c->d_rhits.p);
     HIP_CHECK(hipGetLastError());
     std::vector<uint4> h(n);
-    HIP_CHECK(hipMemcpyAsync(h.data(), c->d_rhits, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipMemcpyAsync(h.data(), c->d_rhits.p, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipStreamSynchronize(c->stream));
     for (uint32_t i = 0; i < n; ++i) {
       out[i].prim = h[i].x;

@@ -76,25 +76,68 @@ struct HostScene {
 
 enum { kNfBuildNever = 0, kNfBuildAlways = 1, kNfBuildAuto = 2 };
 
+// The scene's device arrays, listed once, in the order the upload places
+// them: f(DevScene member, host data, bytes, flags) per array. host_dev_scene
+// and the upload (api.hip mrt_upload_scene_targets) both set the DevScene's
+// pointers from this list, so a new array is one entry here plus its
+// HostScene and DevScene fields.
+enum : unsigned {
+  kArrNullIfEmpty = 1,  // the kernels test the pointer: null when the array is empty
+  kArrDeviceOnly = 2,   // the LDS treelet's arrays: not part of host_dev_scene
+};
+template <typename F>
+void for_each_scene_array(const HostScene& s, F&& f) {
+  auto vec = [&](auto field, const auto& v, unsigned flags = 0) { f(field, v.data(), v.size() * sizeof(v[0]), flags); };
+  vec(&DevScene::slots, s.slots);
+  vec(&DevScene::slots_tl, s.slots_tl, kArrDeviceOnly);
+  vec(&DevScene::tlet, s.tlet, kArrDeviceOnly);
+  vec(&DevScene::inst_inv, s.inst_inv);
+  vec(&DevScene::inst_fwd, s.inst_fwd);
+  vec(&DevScene::inst_mat, s.inst_mat);
+  vec(&DevScene::model_mat, s.model_mat);
+  vec(&DevScene::sph, s.sph);
+  vec(&DevScene::sph_mat, s.sph_mat);
+  vec(&DevScene::tri_shade, s.tri_shade);
+  vec(&DevScene::materials, s.materials);
+  vec(&DevScene::textures, s.textures);
+  vec(&DevScene::texels, s.texels);
+  vec(&DevScene::vol_nid, s.vol_nid);
+  vec(&DevScene::vol_mat, s.vol_mat);
+  vec(&DevScene::ln_table, s.ln_table, kArrNullIfEmpty);
+  vec(&DevScene::surf_ops, s.surf_ops);
+  vec(&DevScene::bg_faces, s.bg_faces);
+  f(&DevScene::bg_m, &s.bg_m[0], sizeof(s.bg_m), 0u);
+  vec(&DevScene::vnf_leaf, s.vnf_leaf);
+  vec(&DevScene::eve, s.eve);
+  vec(&DevScene::tri_tb, s.tri_tb, kArrNullIfEmpty);
+}
+
+// Where the upload puts the arrays: 256-byte-aligned sections, in the list's
+// order, inside one device allocation of total + 256 bytes.
+struct ScenePlan {
+  std::vector<size_t> off;  // per list entry
+  size_t total = 0;         // what mrt_scene_device_bytes reports
+};
+inline ScenePlan plan_scene(const HostScene& s) {
+  ScenePlan p;
+  for_each_scene_array(s, [&](auto, const void*, size_t bytes, unsigned) {
+    p.off.push_back(p.total);
+    p.total += (bytes + 255) & ~(size_t)255;
+  });
+  return p;
+}
+
 // The kernel-visible scene over the HostScene's own vectors (no treelet, no
 // debug record): what the walk's host callers pass to the device headers'
 // functions (tools/slab_check.cpp; valid while `s` lives unchanged), and what
 // mrt_upload_scene starts from before it points the arrays at the device copies.
 inline DevScene host_dev_scene(const HostScene& s) {
   DevScene S{};
-  S.slots = s.slots.data();
+  for_each_scene_array(s, [&](auto field, auto* data, size_t bytes, unsigned flags) {
+    if (!(flags & kArrDeviceOnly)) S.*field = bytes || !(flags & kArrNullIfEmpty) ? data : nullptr;
+  });
   S.world_begin = s.world_begin;
   S.world_end = s.world_end;
-  S.inst_inv = s.inst_inv.data();
-  S.inst_fwd = s.inst_fwd.data();
-  S.inst_mat = s.inst_mat.data();
-  S.model_mat = s.model_mat.data();
-  S.sph = s.sph.data();
-  S.sph_mat = s.sph_mat.data();
-  S.tri_shade = s.tri_shade.data();
-  S.materials = s.materials.data();
-  S.textures = s.textures.data();
-  S.texels = s.texels.data();
   S.fast_ok = (s.fast_ok ? 1u : 0u) | (s.early_ok ? 2u : 0u);
   S.n_slots = (uint32_t)(s.slots.size() / 4);
   S.n_tris = (uint32_t)(s.tri_shade.size() / (kTriShadeQuads * 4));
@@ -104,25 +147,16 @@ inline DevScene host_dev_scene(const HostScene& s) {
   S.n_materials = (uint32_t)s.materials.size();
   S.n_textures = (uint32_t)s.textures.size();
   S.n_texels = (uint32_t)s.texels.size();
-  S.vol_nid = s.vol_nid.data();
-  S.vol_mat = s.vol_mat.data();
-  S.ln_table = s.ln_table.empty() ? nullptr : s.ln_table.data();
   S.n_vol = (uint32_t)s.vol_nid.size();
-  S.surf_ops = s.surf_ops.data();
   S.n_surf_ops = (uint32_t)s.surf_ops.size();
   S.bg_kind = s.bg_kind;
   for (int k = 0; k < 4; ++k) S.bg_color[k] = s.bg_color[k];
-  S.bg_faces = s.bg_faces.data();
-  S.bg_m = s.bg_m;
   S.nf_ok = s.nf_ok ? 1u : 0u;
   S.nf_world = s.nf_world;
   S.nf_wild_root = s.nf_ok ? s.nf_wild_root : 0u;
-  S.vnf_leaf = s.vnf_leaf.data();
   for (int k = 0; k < 4; ++k) S.vnf_base[k] = s.vnf_base[k];
   S.n_vnf = (uint32_t)(s.vnf_leaf.size() / 2);
   S.nfb = s.nfb;
-  S.eve = s.eve.data();
-  S.tri_tb = s.tri_tb.empty() ? nullptr : s.tri_tb.data();
   S.n_eve = (uint32_t)(s.eve.size() / (kEveQuads * 4));
   return S;
 }
