@@ -63,6 +63,7 @@ def lib() -> C.CDLL:
         "orc_blas_count": (I64, [P]),
         "orc_export_blas": (I64, [P, I64, up, fp, U64]),
         "orc_trace_rays": (I, [P, fp, U32, F, F, P]),
+        "orc_shade_rays": (I, [P, fp, U32, F, F, U64, P]),
         "orc_render": (I, [P, U32, U32, U32, U32, U64, U32, U32, U32, I, fp, up]),
         "orc_render_pixels": (I, [P, U32, U32, up, U32, U32, U32, U64, U32, I, fp, up]),
         "orc_bench_reference_mode": (C.c_double, [P, U32, U32, U32, U64, U32, I, fp, up, U32, U32, U32]),
@@ -257,6 +258,17 @@ class Scene:
         out = np.zeros((r.shape[0], 4), dtype=np.uint32)
         self._chk(lib().orc_trace_rays(self.h, _fp(r), r.shape[0], t_min, t_max, out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def shade_rays(self, rays, t_min=0.001, t_max=float("inf"), seed=1):
+        """One step of Camera::trace per ray (orc_shade_rays): the record array
+        massrt.Context.shade_rays returns (its dtype, not a copy of it)."""
+        from massrt import SHADE_DTYPE  # constants only: the product's library is not loaded
+
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        n = r.shape[0]
+        out = np.zeros(max(n, 1), dtype=SHADE_DTYPE)
+        self._chk(lib().orc_shade_rays(self.h, _fp(r), n, t_min, t_max, seed, out.ctypes.data_as(C.c_void_p)))
+        return out[:n]
 
     def render(self, width, height, spp_begin=0, spp_count=1, seed=1, max_depth=50, shard_index=0, shard_count=1,
                threads=0, accum=None):

@@ -20,6 +20,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 namespace orc {
@@ -1554,6 +1555,7 @@ int orc_add_volume(orc_scene* s, float cx, float cy, float cz, float r, float de
     auto* v = new Volume();
     v->center = V3{cx, cy, cz}, v->radius = r, v->neg_inv_density = -1.0f / density;
     v->material = std::make_shared<Isotrophic>(V3{ar, ag, ab});
+    s->materials.push_back(v->material);  // listed like any other (the device's mrt_volume.material)
     v->id = s->n_volumes++;
     s->world.objects.push_back(Obj(v));
     return 0;
@@ -1647,6 +1649,50 @@ int orc_trace_rays(orc_scene* s, const float* rays, uint32_t n, float tmin, floa
       } else {
         out[i] = orc_hit{0, 0, 0.0f, 0};
       }
+    }
+    std::lock_guard<std::mutex> g(s->mu);
+    s->counters.add(c.cnt);
+    return 0;
+  });
+}
+
+static_assert(sizeof(orc_shade_out) == 88, "orc_shade_out is mrt_shade_out: 22 words");
+// One step of Camera::trace (world.rs:65-79) per ray: intersect, emit,
+// scatter on one stream, through the same objects trace() above walks.
+int orc_shade_rays(orc_scene* s, const float* rays, uint32_t n, float tmin, float tmax, uint64_t seed,
+                   orc_shade_out* out) {
+  return guard([&] {
+    std::unordered_map<const Material*, uint32_t> index;
+    for (size_t k = 0; k < s->materials.size(); ++k) index.emplace(s->materials[k].get(), (uint32_t)k);
+    Ctx c;
+    for (uint32_t i = 0; i < n; ++i) {
+      Ray r{v3p(rays + 6 * (size_t)i), v3p(rays + 6 * (size_t)i + 3)};
+      PathRng rng(seed, i, 0xFFFFFFFDu);  // massrt.h mrt_shade_rays
+      c.rng = &rng;
+      orc_shade_out w;
+      memset(&w, 0, sizeof(w));
+      Hit hit;
+      if (s->world.intersect(r, tmin, tmax, hit, c)) {
+        V3 emitted{0, 0, 0};
+        hit.material->emit(hit, c, emitted);
+        Scatter sc;
+        const bool cont = hit.material->scatter(r, hit, c, sc);
+        w.prim = hit.prim, w.container = hit.container, w.t = hit.t;
+        w.flags = (hit.front_face ? ORC_SHADE_FRONT_FACE : 0u) | (hit.has_uv ? ORC_SHADE_HAS_UV : 0u) |
+                  (cont ? ORC_SHADE_SCATTERED : 0u);
+        w.point[0] = hit.point.x, w.point[1] = hit.point.y, w.point[2] = hit.point.z;
+        w.normal[0] = hit.normal.x, w.normal[1] = hit.normal.y, w.normal[2] = hit.normal.z;
+        if (hit.has_uv) w.uv[0] = hit.uv.x, w.uv[1] = hit.uv.y;
+        auto at = index.find(hit.material);
+        w.material = at == index.end() ? 0xFFFFFFFFu : at->second;  // a builtin scene's materials are not listed
+        w.emitted[0] = emitted.x, w.emitted[1] = emitted.y, w.emitted[2] = emitted.z;
+        if (cont) {
+          w.attenuation[0] = sc.attenuation.x, w.attenuation[1] = sc.attenuation.y, w.attenuation[2] = sc.attenuation.z;
+          const V3 d = sc.scattered.direction;
+          w.direction[0] = d.x, w.direction[1] = d.y, w.direction[2] = d.z;
+        }
+      }
+      out[i] = w;
     }
     std::lock_guard<std::mutex> g(s->mu);
     s->counters.add(c.cnt);

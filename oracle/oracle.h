@@ -34,6 +34,19 @@ typedef struct {
   uint32_t front_face;
 } orc_hit;
 
+// One ray shaded one step: field for field mrt_shade_out (include/massrt.h).
+#define ORC_SHADE_FRONT_FACE 1u
+#define ORC_SHADE_HAS_UV 2u
+#define ORC_SHADE_SCATTERED 4u
+typedef struct {
+  uint32_t prim, container;
+  float t;
+  uint32_t flags;
+  float point[3], normal[3], uv[2];
+  uint32_t material;
+  float emitted[3], attenuation[3], direction[3];
+} orc_shade_out;
+
 const char* orc_last_error(void);
 
 // scene construction ---------------------------------------------------------
@@ -58,6 +71,7 @@ int orc_fallback(orc_scene* s, float r, float g, float b, float a, uint32_t surf
 int orc_background_cubemap(orc_scene* s, const uint32_t* faces, const float* rotation);
 int orc_add_sphere(orc_scene* s, uint32_t material, float cx, float cy, float cz, float radius);
 // geom.rs:595-653 Volume over a Sphere target with an Isotrophic(albedo) material
+// (which joins the material list here, as the device's mrt_volume.material does)
 int orc_add_volume(orc_scene* s, float cx, float cy, float cz, float radius, float density, float ar, float ag,
                    float ab);
 int orc_add_triangle(orc_scene* s, uint32_t material, const float* abc);
@@ -82,6 +96,16 @@ int64_t orc_export_blas(orc_scene* s, int64_t blas, uint32_t* kinds_ids, float* 
 
 // hot path ---------------------------------------------------------------------
 int orc_trace_rays(orc_scene* s, const float* rays, uint32_t n, float tmin, float tmax, orc_hit* out);
+// The shading probe (mrt_shade_rays): one step of Camera::trace (world.rs:65-79)
+// per ray, through the objects orc_render uses. Ray i draws from one stream
+// keyed (seed, i, 0xFFFFFFFD): World::intersect's draws (Volume, Mix alpha),
+// then Hit::emit's, then Hit::scatter's. `material` is the index of
+// Hit::material in the scene's material list (orc_material / orc_mix /
+// orc_add_volume in call order). A miss is all zeros; uv is zero where the hit
+// has none, attenuation and direction are zero where the material does not
+// scatter.
+int orc_shade_rays(orc_scene* s, const float* rays, uint32_t n, float tmin, float tmax, uint64_t seed,
+                   orc_shade_out* out);
 // Deterministic render: samples [spp_begin, spp_begin+spp_count) of every pixel
 // of the shard added in sample order (same contract as mrt_render).
 int orc_render(orc_scene* s, uint32_t W, uint32_t H, uint32_t spp_begin, uint32_t spp_count, uint64_t seed,
