@@ -114,6 +114,9 @@ impl SceneSink {
     }
 }
 
+/// One view of `Context::render_views`: a camera and the seed of its samples' streams.
+pub type View = mrt_view;
+
 /// One GPU context (mrt_ctx); destroyed on drop.
 pub struct Context {
     raw: *mut mrt_ctx,
@@ -185,6 +188,20 @@ impl Context {
         let n = (args.width * args.height) as usize;
         assert!(rgb.len() >= 3 * n && bounces.len() >= n);
         self.check(unsafe { mrt_render(self.raw, args, rgb.as_mut_ptr(), bounces.as_mut_ptr()) })
+    }
+
+    /// Many cameras of the uploaded scene in one wavefront render
+    /// (mrt_render_views): view v exactly `mrt_set_camera(views[v].camera)` +
+    /// `render` with `views[v].seed`, ADDED into view v's own frame, `rgb`
+    /// (n*w*h*3) and `bounces` (n*w*h) holding the frames one behind the other.
+    /// `args.seed` is not used; the context's camera is neither needed nor changed.
+    pub fn render_views(&self, args: &mrt_render_args, views: &[View], rgb: &mut [f32], bounces: &mut [u32])
+        -> Result<(), MrtError> {
+        let n = views.len() * (args.width as usize) * (args.height as usize);
+        assert!(rgb.len() >= 3 * n && bounces.len() >= n);
+        self.check(unsafe {
+            mrt_render_views(self.raw, args, views.as_ptr(), views.len() as u32, rgb.as_mut_ptr(), bounces.as_mut_ptr())
+        })
     }
 
     pub fn prepass(&mut self, w: u32, h: u32, seed: u64, albedo: &mut [f32], normal: &mut [f32])

@@ -269,6 +269,14 @@ pub struct mrt_render_args {
     pub flags: u32,
 }
 
+/// One view of mrt_render_views: a camera and the seed of its samples' streams.
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct mrt_view {
+    pub camera: mrt_camera,
+    pub seed: u64,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
 pub struct mrt_hit {
@@ -402,6 +410,11 @@ extern "C" {
         -> i32;
     pub fn mrt_render_device(ctx: *mut mrt_ctx, args: *const mrt_render_args, d_accum_rgb: *mut f32,
                              d_accum_bounces: *mut u32, hip_stream: *mut c_void) -> i32;
+    pub fn mrt_render_views(ctx: *mut mrt_ctx, args: *const mrt_render_args, views: *const mrt_view, n_views: u32,
+                            accum_rgb: *mut f32, accum_bounces: *mut u32) -> i32;
+    pub fn mrt_render_views_device(ctx: *mut mrt_ctx, args: *const mrt_render_args, views: *const mrt_view,
+                                   n_views: u32, d_accum_rgb: *mut f32, d_accum_bounces: *mut u32,
+                                   hip_stream: *mut c_void) -> i32;
     pub fn mrt_trace_rays(ctx: *mut mrt_ctx, rays: *const f32, n: u32, t_min: f32, t_max: f32, out: *mut mrt_hit)
         -> i32;
     pub fn mrt_get_counters(ctx: *mut mrt_ctx, out: *mut mrt_counters) -> i32;

@@ -265,6 +265,12 @@ typedef struct {
 #define MRT_RENDER_FUSED 8u        /* one persistent k_render (trace + shade per lane) instead of the
                                       k_trace/k_shade wavefront loop; same results, slower at 108 VGPRs */
 
+/* One view of mrt_render_views: a camera and the seed of its samples' streams. */
+typedef struct {
+  mrt_camera camera;
+  uint64_t seed;
+} mrt_view;
+
 /* Closest hit of one ray (parity entry point). */
 typedef struct {
   uint32_t prim;      /* MRT_REF(kind, index) of the primitive hit, or NONE */
@@ -360,6 +366,37 @@ int mrt_render(mrt_ctx* ctx, const mrt_render_args* args, float* accum_rgb, uint
  * with the caller's default-stream work) */
 int mrt_render_device(mrt_ctx* ctx, const mrt_render_args* args, float* d_accum_rgb,
                       uint32_t* d_accum_bounces, void* hip_stream);
+/* Many cameras of the uploaded scene in one call (the frames of a fly-through
+ * or a turntable, a stereo pair, the faces of a cube-map capture, a multi-view
+ * data set; the reference's EXPORT_FRAMES loop, main.rs:104-141, for a world
+ * that does not change). Views v = 0..n_views-1, each exactly the render
+ *   mrt_set_camera(&views[v].camera); args.seed = views[v].seed; mrt_render(args)
+ * added into view v's own frame: accum_rgb + v*width*height*3,
+ * accum_bounces + v*width*height. args->seed is not used; width, height,
+ * spp_begin, spp_count, max_depth, shard_index/count and flags apply to every
+ * view. All views run through one wavefront loop: their paths fill the path
+ * pool together and drain once.
+ *  - Keys: sample s of pixel p of view v draws from the stream of
+ *    (views[v].seed, p, s), p = y*width + x within the view. Two views with
+ *    equal camera and seed are equal bit for bit, and one call, n_views calls,
+ *    chunks and shards give the same bits.
+ *  - The call neither needs nor changes the context's camera (mrt_set_camera).
+ *    `views` (host memory in both forms) is consumed when the call returns.
+ *    The _device form is ordered on `hip_stream` as mrt_render_device is and
+ *    does not wait for the render.
+ *  - Before anything is enqueued: views == NULL, n_views == 0,
+ *    n_views*width*height >= 2^32 or MRT_RENDER_FUSED (it renders one camera)
+ *    is MRT_ERR_INVALID; no scene uploaded is MRT_ERR_STATE; buffers that do
+ *    not fit the device are MRT_ERR_NOMEM as for mrt_render. The other
+ *    MRT_RENDER_* flags work as for one frame.
+ *  - On a multi-device context both forms run on device 0, as
+ *    mrt_render_device does; a caller spreads views or shards over devices.
+ *  - Each view's slice is an ordinary width x height frame: mrt_tonemap_device
+ *    and mrt_denoise_device take it by pointer offset. */
+int mrt_render_views(mrt_ctx* ctx, const mrt_render_args* args, const mrt_view* views, uint32_t n_views,
+                     float* accum_rgb, uint32_t* accum_bounces);
+int mrt_render_views_device(mrt_ctx* ctx, const mrt_render_args* args, const mrt_view* views, uint32_t n_views,
+                            float* d_accum_rgb, uint32_t* d_accum_bounces, void* hip_stream);
 /* rays: n x {ox,oy,oz,dx,dy,dz} host floats; out: n hits. Draws during the
  * traversal (Volume, Mix alpha tests) use ray i's stream keyed
  * (seed 0, i, sample 0xFFFFFFFE). */

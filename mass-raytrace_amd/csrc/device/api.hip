@@ -31,6 +31,19 @@ void ctx_set_error(mrt_ctx* c, const std::string& msg) {
 }
 int massrt_ctx_device(const mrt_ctx* c) { return c ? c->device : -1; }  // device 0's for a multi-device context
 
+// The ABI's camera as the kernels take it (mrt_set_camera, mrt_render_views).
+DevCamera dev_camera(const mrt_camera& cam) {
+  DevCamera d;
+  d.origin = V3{cam.origin[0], cam.origin[1], cam.origin[2]};
+  d.llc = V3{cam.lower_left_corner[0], cam.lower_left_corner[1], cam.lower_left_corner[2]};
+  d.horizontal = V3{cam.horizontal[0], cam.horizontal[1], cam.horizontal[2]};
+  d.vertical = V3{cam.vertical[0], cam.vertical[1], cam.vertical[2]};
+  d.u = V3{cam.u[0], cam.u[1], cam.u[2]};
+  d.v = V3{cam.v[0], cam.v[1], cam.v[2]};
+  d.lens_radius = cam.lens_radius;
+  return d;
+}
+
 namespace {
 
 // Re-derives the tuning (options.h derive_tuning) and applies what depends on it in the context.
@@ -262,15 +275,7 @@ int mrt_set_camera(mrt_ctx* c, const mrt_camera* cam) {
   MRT_EACH(c, mrt_set_camera(c, cam));
   return guarded(c, [&] {
     if (!cam) throw ApiError{MRT_ERR_INVALID, "null camera"};
-    DevCamera d;
-    d.origin = V3{cam->origin[0], cam->origin[1], cam->origin[2]};
-    d.llc = V3{cam->lower_left_corner[0], cam->lower_left_corner[1], cam->lower_left_corner[2]};
-    d.horizontal = V3{cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]};
-    d.vertical = V3{cam->vertical[0], cam->vertical[1], cam->vertical[2]};
-    d.u = V3{cam->u[0], cam->u[1], cam->u[2]};
-    d.v = V3{cam->v[0], cam->v[1], cam->v[2]};
-    d.lens_radius = cam->lens_radius;
-    c->cam = d;
+    c->cam = dev_camera(*cam);
     c->has_camera = true;
   });
 }

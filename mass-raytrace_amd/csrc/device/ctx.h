@@ -106,7 +106,10 @@ struct mrt_ctx {
   float4* slot_rd = nullptr;
   hipEvent_t tev[2] = {nullptr, nullptr};
 
-  std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>, DevBuf<uint32_t>> pixlists;
+  // pixel lists by (W, H, shard_index, shard_count, n_views); n_views 0: one frame's list
+  std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t>, DevBuf<uint32_t>> pixlists;
+  DevBuf<DevView> views;  // the view table of the last mrt_render_views (grown on demand; the kernels only read it)
+  std::vector<DevView> views_h;  // its host copy, the upload's source
   // host-buffer render staging
   DevBuf<float> d_acc_rgb;
   DevBuf<uint32_t> d_acc_b;
@@ -204,7 +207,11 @@ void release_pool(mrt_ctx* c);  // frees the path pool; the caller has synchroni
 void ensure_pool(mrt_ctx* c, size_t P);
 void ensure_slots(mrt_ctx* c, size_t n);
 std::vector<uint32_t> shard_pixel_list(uint32_t W, uint32_t H, uint32_t si, uint32_t sc);
-std::pair<uint32_t*, uint32_t> pixlist(mrt_ctx* c, uint32_t W, uint32_t H, uint32_t si, uint32_t sc);
+std::pair<uint32_t*, uint32_t> pixlist(mrt_ctx* c, uint32_t W, uint32_t H, uint32_t si, uint32_t sc,
+                                       uint32_t n_views = 0);
 void mark_ctx_busy(mrt_ctx* c, hipStream_t st);
 void render_device(mrt_ctx* c, const mrt_render_args* a, float* d_rgb, uint32_t* d_b, hipStream_t st);
+void render_views_device(mrt_ctx* c, const mrt_render_args* a, const mrt_view* views, uint32_t n_views, float* d_rgb,
+                         uint32_t* d_b, hipStream_t st);
+mrt::DevCamera dev_camera(const mrt_camera& cam);
 void resolve_kernel_timing(mrt_ctx* c);

@@ -2,6 +2,7 @@
 // per-chunk parameters) and the wave / workgroup helpers its kernels share.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 
 #include "path.h"
 
@@ -67,7 +68,27 @@ struct RenderParams {
   uint32_t shade_bin;    // k_shade: survivors grouped by material kind and direction in the next pool (option shade_bin)
 };
 
-constexpr float kTmin = 0.001f;          // World::intersect(ray, 0.001, INFINITY) (main.rs trace)
+// One view of a batch (mrt_render_views): its camera and the seed of its
+// samples' streams. The context keeps the batch's table on the device; the
+// kernels only read it.
+struct alignas(16) DevView {
+  mrt::DevCamera cam;
+  uint32_t pad_;
+  unsigned long long seed;
+};
+static_assert(sizeof(DevView) == 96 && offsetof(DevView, seed) == 80, "DevView: 96 B, the seed on an 8-B boundary");
+
+// Where the view variants of the generation kernels take the camera from: the
+// render's pixel list then holds global pixels P = v pix_per_view + p
+// (loop.h view_split). Its own kernel argument; RenderParams stays as it is.
+struct ViewTable {
+  const DevView* views;
+  uint32_t pix_per_view;  // W H
+  uint32_t n_views;
+  uint32_t* dbg;  // MRT_IDX's record (DevScene::dbg)
+};
+
+constexpr float kTmin = 0.001f;         // World::intersect(ray, 0.001, INFINITY) (main.rs trace)
 constexpr uint32_t kIdle = 0xFFFFFFFFu;  // Trav.ray of a lane without a ray
 
 namespace {

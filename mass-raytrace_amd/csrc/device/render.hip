@@ -29,25 +29,51 @@ namespace {
 #endif
 constexpr int kShadeBlock = MRT_SHADE_BLOCK;
 
-__device__ __forceinline__ void gen_work(const DevCamera& cam, const RenderParams& rp, uint32_t g, float4& ro,
-                                         float4& rd, uint4& rs) {
+// Where a work item's camera comes from (CAM): the render's one camera, by
+// value in the kernel's arguments, or a table of views (mrt_render_views).
+// work_camera gives the camera and the stream seed of pixel-list entry p and
+// leaves in p the pixel within its frame.
+__device__ __forceinline__ const DevCamera& work_camera(const DevCamera& cam, const RenderParams& rp, uint32_t& p,
+                                                        unsigned long long& seed) {
+  seed = rp.seed;
+  return cam;
+}
+// The entry is a global pixel P = v W H + p (loop.h view_split): view v's
+// camera and seed, loaded per lane from the table (a few hundred bytes that
+// every wave reads: cache hits), and p as view v's own render has it, so the
+// path draws from the stream of that render.
+__device__ __forceinline__ const DevCamera& work_camera(const ViewTable& t, const RenderParams& rp, uint32_t& p,
+                                                        unsigned long long& seed) {
+  const ViewPixel vp = view_split(p, t.pix_per_view);
+  const DevView& w = t.views[MRT_IDX(t, vp.v, t.n_views, 26)];
+  p = vp.p;
+  seed = w.seed;
+  return w.cam;
+}
+
+template <typename CAM>
+__device__ __forceinline__ void gen_work(const CAM& cam, const RenderParams& rp, uint32_t g, float4& ro, float4& rd,
+                                         uint4& rs) {
   // work items run sample-minor: the samples of one pixel are consecutive
   // (camera rays of a wave nearly equal), and the results slab is laid out
   // the same way, g = pixel * spp + sample
   uint32_t lp = g / rp.spp;
   uint32_t s_local = g - lp * rp.spp;
   uint32_t p = rp.pixlist[lp];  // lp < n_pix by construction (g < G)
+  unsigned long long seed;
+  const DevCamera& c = work_camera(cam, rp, p, seed);
   uint32_t y = p / rp.W, x = p - y * rp.W;
-  PathRng rng = path_rng(rp.seed, p, rp.sample_base + s_local);
+  PathRng rng = path_rng(seed, p, rp.sample_base + s_local);
   V3 o, d;
-  camera_ray(cam, x, y, rp.W, rp.H, rng, o, d);
+  camera_ray(c, x, y, rp.W, rp.H, rng, o, d);
   ro = make_float4(o.x, o.y, o.z, __uint_as_float(g));
   rd = make_float4(d.x, d.y, d.z, __uint_as_float(0u));
   rs = rng_pack(rng);
 }
 
 // The new camera path of work item g into slot i of a pool.
-__device__ __forceinline__ void gen_path(const DevCamera& cam, const RenderParams& rp, const PathBufs& out, uint32_t g,
+template <typename CAM>
+__device__ __forceinline__ void gen_path(const CAM& cam, const RenderParams& rp, const PathBufs& out, uint32_t g,
                                          uint32_t i) {
   float4 ro, rd;
   uint4 rs;
@@ -64,6 +90,12 @@ __global__ __launch_bounds__(kBlock) void k_generate(DevCamera cam, RenderParams
   uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n0) return;
   gen_path(cam, rp, out, base + i, i);
+}
+__global__ __launch_bounds__(kBlock) void k_generate_views(ViewTable views, RenderParams rp, PathBufs out,
+                                                           uint32_t base, uint32_t n0) {
+  uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n0) return;
+  gen_path(views, rp, out, base + i, i);
 }
 
 // Lagged status read of a queue (host loop, one per batch): the fields the
@@ -109,7 +141,8 @@ __global__ void k_reserve(Ctrl* ctrl, uint32_t cur, uint32_t* work, uint32_t G, 
 // ... and generate them (camera rays of consecutive work items, i.e. pixel
 // order): the next k_trace finds the new paths together behind the
 // survivors instead of scattered among them one per finished slot.
-__global__ __launch_bounds__(kBlock) void k_refill(DevCamera cam, RenderParams rp, PathBufs out, const Ctrl* ctrl) {
+template <typename CAM>
+__device__ __forceinline__ void refill(const CAM& cam, const RenderParams& rp, const PathBufs& out, const Ctrl* ctrl) {
   const uint32_t m = ctrl->gen_count, slot = ctrl->gen_slot, base = ctrl->gen_base;
   const uint32_t mv = ctrl->gen_move, src = ctrl->gen_move_src, dst = ctrl->gen_move_dst;
   for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < mv; j += gridDim.x * kBlock) {
@@ -125,6 +158,13 @@ __global__ __launch_bounds__(kBlock) void k_refill(DevCamera cam, RenderParams r
   }
   for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < m; j += gridDim.x * kBlock)
     gen_path(cam, rp, out, base + j, slot + j);
+}
+__global__ __launch_bounds__(kBlock) void k_refill(DevCamera cam, RenderParams rp, PathBufs out, const Ctrl* ctrl) {
+  refill(cam, rp, out, ctrl);
+}
+__global__ __launch_bounds__(kBlock) void k_refill_views(ViewTable views, RenderParams rp, PathBufs out,
+                                                         const Ctrl* ctrl) {
+  refill(views, rp, out, ctrl);
 }
 
 // k_shade only shades and compacts: new camera rays go in behind the
@@ -555,24 +595,17 @@ void ensure_slots(mrt_ctx* c, size_t n) {
 // MRT_TILE x MRT_TILE tiles in raster order; shard si of sc owns t % sc == si;
 // pixels of a tile in raster order, y = 0 the bottom row (main.rs:253-263)
 std::vector<uint32_t> shard_pixel_list(uint32_t W, uint32_t H, uint32_t si, uint32_t sc) {
-  uint32_t tx = (W + MRT_TILE - 1) / MRT_TILE, ty = (H + MRT_TILE - 1) / MRT_TILE;
-  std::vector<uint32_t> list;
-  for (uint32_t t = si; t < tx * ty; t += sc) {
-    uint32_t bx = (t % tx) * MRT_TILE, by = (t / tx) * MRT_TILE;
-    for (uint32_t py = 0; py < MRT_TILE; ++py)
-      for (uint32_t px = 0; px < MRT_TILE; ++px) {
-        uint32_t x = bx + px, y = by + py;
-        if (x < W && y < H) list.push_back(y * W + x);
-      }
-  }
-  return list;
+  return shard_list(W, H, si, sc, MRT_TILE);
 }
 
-std::pair<uint32_t*, uint32_t> pixlist(mrt_ctx* c, uint32_t W, uint32_t H, uint32_t si, uint32_t sc) {
-  auto key = std::make_tuple(W, H, si, sc);
+// n_views == 0: the shard's list of one frame; else that list once per view
+// as global pixels (loop.h view_list), for mrt_render_views.
+std::pair<uint32_t*, uint32_t> pixlist(mrt_ctx* c, uint32_t W, uint32_t H, uint32_t si, uint32_t sc, uint32_t n_views) {
+  auto key = std::make_tuple(W, H, si, sc, n_views);
   auto it = c->pixlists.find(key);
   if (it == c->pixlists.end()) {
-    const std::vector<uint32_t> list = shard_pixel_list(W, H, si, sc);
+    std::vector<uint32_t> list = shard_pixel_list(W, H, si, sc);
+    if (n_views) list = view_list(list, n_views, W * H);
     DevBuf<uint32_t> d;
     HIP_CHECK(d.alloc(list.size()));
     if (d.p) HIP_CHECK(hipMemcpy(d.p, list.data(), list.size() * 4, hipMemcpyHostToDevice));
@@ -622,13 +655,15 @@ struct Pass {
   bool count, simple;
   uint32_t finish_paths;  // drain hand-off threshold (0: never)
   ShadeFn shade;
+  ViewTable views;  // views.views != nullptr: a batch of views, the cameras from this table (the context's otherwise)
 };
 
 // The argument and state errors of a render, before anything is enqueued.
-void check_render_args(const mrt_ctx* c, const mrt_render_args* a) {
+// (A batch of views brings its own cameras: need_camera false.)
+void check_render_args(const mrt_ctx* c, const mrt_render_args* a, bool need_camera = true) {
   if (!a) throw ApiError{MRT_ERR_INVALID, "null render args"};
   if (!c->has_scene) throw ApiError{MRT_ERR_STATE, "no scene uploaded"};
-  if (!c->has_camera) throw ApiError{MRT_ERR_STATE, "no camera set"};
+  if (need_camera && !c->has_camera) throw ApiError{MRT_ERR_STATE, "no camera set"};
   if (a->width == 0 || a->height == 0) throw ApiError{MRT_ERR_INVALID, "empty image"};
   if ((uint64_t)a->width * a->height >= (1ull << 32)) throw ApiError{MRT_ERR_INVALID, "image too large"};
   if (a->shard_index >= (a->shard_count ? a->shard_count : 1))
@@ -653,7 +688,7 @@ void check_render_flags(const mrt_ctx* c, const mrt_render_args* a) {
 // (acc_done, on the caller's stream; the kernels read nothing else the
 // caller's stream writes). The shared work counter starts behind the chunk's
 // first n0 paths, which k_generate deals over the queues' pools.
-void fork_queues(mrt_ctx* c, const RenderParams& rp) {
+void fork_queues(mrt_ctx* c, const RenderParams& rp, const Pass& p) {
   const int K = c->tun.queues;
   const uint32_t n0 = (uint32_t)std::min<size_t>(rp.G, c->pool_cap);
   HIP_CHECK(hipStreamWaitEvent(c->q[0].stream, c->acc_done, 0));
@@ -667,8 +702,11 @@ void fork_queues(mrt_ctx* c, const RenderParams& rp) {
     const Ctrl init = ctrl_init(nk);
     HIP_CHECK(hipMemcpyAsync(q.ctrl.p, &init, sizeof(Ctrl), hipMemcpyHostToDevice, q.stream));
     if (nk) {
-      hipLaunchKernelGGL(k_generate, dim3((nk + kBlock - 1) / kBlock), dim3(kBlock), 0, q.stream, c->cam, rp,
-                         q.bufs[0], base, nk);
+      const dim3 grid((nk + kBlock - 1) / kBlock);
+      if (p.views.views)
+        hipLaunchKernelGGL(k_generate_views, grid, dim3(kBlock), 0, q.stream, p.views, rp, q.bufs[0], base, nk);
+      else
+        hipLaunchKernelGGL(k_generate, grid, dim3(kBlock), 0, q.stream, c->cam, rp, q.bufs[0], base, nk);
       HIP_CHECK(hipGetLastError());
     }
     base += nk;
@@ -691,8 +729,12 @@ void enqueue_batch(mrt_ctx* c, Queue& q, QueueLoop& L, const RenderParams& rp, c
     HIP_CHECK(hipGetLastError());
     if (!L.exhausted || rp.shade_bin == 2) {  // new paths behind the survivors (shade_bin 2: and the pool's ends joined)
       hipLaunchKernelGGL(k_reserve, dim3(1), dim3(64), 0, q.stream, q.ctrl.p, cur, c->work.p, rp.G, rp.pool_cap);
-      hipLaunchKernelGGL(k_refill, dim3(c->refill_grid), dim3(kBlock), 0, q.stream, c->cam, rp, q.bufs[cur ^ 1],
-                         (const Ctrl*)q.ctrl.p);
+      if (p.views.views)
+        hipLaunchKernelGGL(k_refill_views, dim3(c->refill_grid), dim3(kBlock), 0, q.stream, p.views, rp,
+                           q.bufs[cur ^ 1], (const Ctrl*)q.ctrl.p);
+      else
+        hipLaunchKernelGGL(k_refill, dim3(c->refill_grid), dim3(kBlock), 0, q.stream, c->cam, rp, q.bufs[cur ^ 1],
+                           (const Ctrl*)q.ctrl.p);
       HIP_CHECK(hipGetLastError());
     }
     const hipEvent_t m2 = t.stamp(q.stream);
@@ -762,20 +804,15 @@ void join_queues(mrt_ctx* c, hipStream_t st) {
 
 }  // namespace
 
-void render_device(mrt_ctx* c, const mrt_render_args* a, float* d_rgb, uint32_t* d_b, hipStream_t st) {
-  check_render_args(c, a);
-  if (a->spp_count == 0) return;
-  auto pl = pixlist(c, a->width, a->height, a->shard_index, a->shard_count ? a->shard_count : 1);
-  const uint32_t n_pix = pl.second;
-  if (n_pix == 0) return;
-  check_render_flags(c, a);
+namespace {
+
+// The wavefront loop over a pixel list, every step from plan_buffers on: what
+// a render of the context's camera and a render of a batch of views
+// (views.views != nullptr; the list then holds global pixels) share.
+void render_wavefront(mrt_ctx* c, const mrt_render_args* a, const uint32_t* pixlist_d, uint32_t n_pix,
+                      uint32_t spp_chunk, const ViewTable& views, float* d_rgb, uint32_t* d_b, hipStream_t st) {
   const bool count = (a->flags & MRT_RENDER_COUNTERS) != 0;
   const bool simple = (a->flags & MRT_RENDER_SIMPLE_TRACE) != 0;
-  uint32_t spp_chunk = first_chunk(a->spp_count, c->tun.results_max, n_pix);
-  if ((a->flags & MRT_RENDER_FUSED) && !simple) {
-    render_fused(c, a, pl.first, n_pix, spp_chunk, d_rgb, d_b, st);
-    return;
-  }
   plan_buffers(c, n_pix, spp_chunk, true);
   Stamps stamps{c, (a->flags & MRT_RENDER_TIME_KERNELS) != 0};
   if (stamps.timing && c->pend_marks.size() + c->pend_fin.size() > kMaxPendingMarks) resolve_kernel_timing(c);
@@ -783,19 +820,78 @@ void render_device(mrt_ctx* c, const mrt_render_args* a, float* d_rgb, uint32_t*
   // draws or composite surfaces; its lane-ray slots are allocated here, before
   // any queue runs (ensure_slots reallocates)
   const bool can_finish = !c->facts.trav_rng && !c->scene_ext && !simple;
-  const Pass p{count, simple, can_finish ? c->tun.finish_paths : 0u, shade_kernel(count, c->scene_ext, c->tun.shade_wpe)};
+  const Pass p{count, simple, can_finish ? c->tun.finish_paths : 0u, shade_kernel(count, c->scene_ext, c->tun.shade_wpe),
+               views};
   if (p.finish_paths) ensure_slots(c, (size_t)finish_grid(c, count) * kBlock * kMaxQueues);
   for (uint32_t done = 0; done < a->spp_count; done += spp_chunk) {
     const uint32_t cs = std::min(spp_chunk, a->spp_count - done);
-    const RenderParams rp = chunk_params(c, a, pl.first, n_pix, done, cs, (uint32_t)c->q[0].cap);
+    const RenderParams rp = chunk_params(c, a, pixlist_d, n_pix, done, cs, (uint32_t)c->q[0].cap);
     if (a->max_depth == 0) continue;  // trace(ray, 0) returns (0, 0) for every sample: nothing to add
-    fork_queues(c, rp);
+    fork_queues(c, rp, p);
     run_queues(c, rp, p, stamps);
     join_queues(c, st);
     stamps.keep();
     accumulate(c, rp, d_rgb, d_b, st);
     HIP_CHECK(hipEventRecord(c->acc_done, st));  // the slab is free again after this
   }
+}
+
+}  // namespace
+
+void render_device(mrt_ctx* c, const mrt_render_args* a, float* d_rgb, uint32_t* d_b, hipStream_t st) {
+  check_render_args(c, a);
+  if (a->spp_count == 0) return;
+  auto pl = pixlist(c, a->width, a->height, a->shard_index, a->shard_count ? a->shard_count : 1);
+  const uint32_t n_pix = pl.second;
+  if (n_pix == 0) return;
+  check_render_flags(c, a);
+  const bool simple = (a->flags & MRT_RENDER_SIMPLE_TRACE) != 0;
+  const uint32_t spp_chunk = first_chunk(a->spp_count, c->tun.results_max, n_pix);
+  if ((a->flags & MRT_RENDER_FUSED) && !simple) {
+    render_fused(c, a, pl.first, n_pix, spp_chunk, d_rgb, d_b, st);
+    return;
+  }
+  render_wavefront(c, a, pl.first, n_pix, spp_chunk, ViewTable{}, d_rgb, d_b, st);
+}
+
+// mrt_render_views_device: one wavefront render over the shard's pixels of
+// every view (loop.h view_list), the cameras and seeds from a table on the
+// device. The pool and the results slab are planned for all views at once, so
+// a batch of small frames fills the pool as one large frame does, and drains
+// once per chunk.
+void render_views_device(mrt_ctx* c, const mrt_render_args* a, const mrt_view* views, uint32_t n_views, float* d_rgb,
+                         uint32_t* d_b, hipStream_t st) {
+  if (!views || n_views == 0) throw ApiError{MRT_ERR_INVALID, "mrt_render_views: no views"};
+  check_render_args(c, a, false);
+  if (!views_fit(n_views, a->width, a->height))
+    throw ApiError{MRT_ERR_INVALID, "mrt_render_views: n_views * width * height must be below 2^32"};
+  if (a->flags & MRT_RENDER_FUSED)
+    throw ApiError{MRT_ERR_INVALID, "mrt_render_views: MRT_RENDER_FUSED renders one camera"};
+  check_render_flags(c, a);
+  if (a->spp_count == 0) return;
+  auto pl = pixlist(c, a->width, a->height, a->shard_index, a->shard_count ? a->shard_count : 1, n_views);
+  const uint32_t n_pix = pl.second;
+  if (n_pix == 0) return;
+  if (a->max_depth == 0) return;  // trace(ray, 0) returns (0, 0) for every sample: nothing to add
+  // the caller's views are consumed here. The host copy stays with the
+  // context: the upload below reads it when queue 0's stream gets there, and
+  // by the next batch it has (that batch's host loop read the status of
+  // kernels behind it)
+  std::vector<DevView>& table = c->views_h;
+  table.resize(n_views);
+  for (uint32_t v = 0; v < n_views; ++v) table[v] = DevView{dev_camera(views[v].camera), 0u, views[v].seed};
+  if (c->views.n < n_views) {
+    if (c->views.p) HIP_CHECK(hipDeviceSynchronize());  // the last batch's kernels may still read the old table
+    HIP_CHECK(c->views.alloc(n_views));
+  }
+  // the table is written on queue 0's stream behind the last render's
+  // accumulate (acc_done: every queue's kernels, the old table's readers, end
+  // before it), and every fork of this render follows on that stream
+  HIP_CHECK(hipStreamWaitEvent(c->q[0].stream, c->acc_done, 0));
+  HIP_CHECK(hipMemcpyAsync(c->views.p, table.data(), (size_t)n_views * sizeof(DevView), hipMemcpyHostToDevice,
+                           c->q[0].stream));
+  const ViewTable vt{c->views.p, a->width * a->height, n_views, c->dbg.p};
+  render_wavefront(c, a, pl.first, n_pix, first_chunk(a->spp_count, c->tun.results_max, n_pix), vt, d_rgb, d_b, st);
 }
 
 // Kernel timing of renders flagged MRT_RENDER_TIME_KERNELS, resolved when the
@@ -847,6 +943,37 @@ int mrt_render(mrt_ctx* c, const mrt_render_args* a, float* rgb, uint32_t* bounc
     HIP_CHECK(hipMemcpyAsync(d_rgb, rgb, np * 12, hipMemcpyHostToDevice, c->stream));
     HIP_CHECK(hipMemcpyAsync(d_b, bounces, np * 4, hipMemcpyHostToDevice, c->stream));
     render_device(c, a, d_rgb, d_b, c->stream);
+    HIP_CHECK(hipMemcpyAsync(rgb, d_rgb, np * 12, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipMemcpyAsync(bounces, d_b, np * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+  });
+}
+
+int mrt_render_views_device(mrt_ctx* c, const mrt_render_args* a, const mrt_view* views, uint32_t n_views,
+                            float* d_rgb, uint32_t* d_b, void* stream) {
+  MRT_DEV0(c, mrt_render_views_device(c, a, views, n_views, d_rgb, d_b, stream));
+  return guarded(c, [&] {
+    if (!d_rgb || !d_b) throw ApiError{MRT_ERR_INVALID, "null accumulation buffer"};
+    render_views_device(c, a, views, n_views, d_rgb, d_b, (hipStream_t)stream);  // NULL: the null stream
+  });
+}
+
+int mrt_render_views(mrt_ctx* c, const mrt_render_args* a, const mrt_view* views, uint32_t n_views, float* rgb,
+                     uint32_t* bounces) {
+  MRT_DEV0(c, mrt_render_views(c, a, views, n_views, rgb, bounces));
+  return guarded(c, [&] {
+    if (!a || !rgb || !bounces) throw ApiError{MRT_ERR_INVALID, "null argument"};
+    if (!views || n_views == 0) throw ApiError{MRT_ERR_INVALID, "mrt_render_views: no views"};
+    if (!views_fit(n_views, a->width, a->height))
+      throw ApiError{MRT_ERR_INVALID, "mrt_render_views: n_views * width * height must be below 2^32"};
+    const size_t np = (size_t)n_views * a->width * a->height;  // the views' frames, one behind the other
+    HIP_CHECK(c->d_acc_rgb.reserve(np * 3));
+    HIP_CHECK(c->d_acc_b.reserve(np));
+    float* d_rgb = c->d_acc_rgb.p;
+    uint32_t* d_b = c->d_acc_b.p;
+    HIP_CHECK(hipMemcpyAsync(d_rgb, rgb, np * 12, hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(hipMemcpyAsync(d_b, bounces, np * 4, hipMemcpyHostToDevice, c->stream));
+    render_views_device(c, a, views, n_views, d_rgb, d_b, c->stream);
     HIP_CHECK(hipMemcpyAsync(rgb, d_rgb, np * 12, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipMemcpyAsync(bounces, d_b, np * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipStreamSynchronize(c->stream));

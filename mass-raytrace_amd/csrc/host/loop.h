@@ -1,14 +1,16 @@
 // loop.h — the integer decisions of the wavefront loop (render.hip): the
 // refill and gap-closing plan of k_reserve, the sizes of the path pool and
-// the results slab, the split of a chunk's first paths over the queues, and
-// what a queue does with a lagged status read. Plain C++, no HIP: every
-// function here runs on the host in tools/loop_check.cpp
-// (tests/test_loop.py); those a kernel also calls carry MRT_HD.
+// the results slab, the pixel lists of a shard and of a batch of views, the
+// split of a chunk's first paths over the queues, and what a queue does with
+// a lagged status read. Plain C++, no HIP: every function here runs on the
+// host in tools/loop_check.cpp (tests/test_loop.py) or tools/views_check.cpp
+// (tests/test_views.py); those a kernel also calls carry MRT_HD.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "../mrt_math.h"
 
@@ -98,6 +100,53 @@ inline SizePlan plan_sizes(uint32_t n_pix, uint32_t spp_chunk, size_t pool_paths
       return SizePlan{P, spp_chunk, false};
     }
   }
+}
+
+// ---- pixel lists (pixlist) --------------------------------------------------
+
+// A shard's pixels p = y W + x: tile x tile tiles in raster order, shard si of
+// sc owns the tiles t with t % sc == si; the pixels of a tile in raster order,
+// y = 0 the bottom row (main.rs:253-263).
+inline std::vector<uint32_t> shard_list(uint32_t W, uint32_t H, uint32_t si, uint32_t sc, uint32_t tile) {
+  const uint32_t tx = (W + tile - 1) / tile, ty = (H + tile - 1) / tile;
+  std::vector<uint32_t> list;
+  for (uint32_t t = si; t < tx * ty; t += sc) {
+    const uint32_t bx = (t % tx) * tile, by = (t / tx) * tile;
+    for (uint32_t py = 0; py < tile; ++py)
+      for (uint32_t px = 0; px < tile; ++px) {
+        const uint32_t x = bx + px, y = by + py;
+        if (x < W && y < H) list.push_back(y * W + x);
+      }
+  }
+  return list;
+}
+
+// A render of n_views views of W x H pixels (mrt_render_views) runs over
+// global pixels P = v W H + p: pixel p of view v, and at once the pixel's
+// place in the caller's buffers, view v's frame behind view v - 1's. They fit
+// 32 bits: n_views W H < 2^32.
+inline bool views_fit(uint64_t n_views, uint32_t W, uint32_t H) {
+  const uint64_t ppv = (uint64_t)W * H;  // < 2^64: no product below overflows
+  return n_views > 0 && ppv > 0 && ppv < (1ull << 32) && n_views < (1ull << 32) && n_views * ppv < (1ull << 32);
+}
+MRT_HD uint32_t view_pixel(uint32_t v, uint32_t p, uint32_t pix_per_view) { return v * pix_per_view + p; }
+struct ViewPixel {
+  uint32_t v, p;
+};
+MRT_HD ViewPixel view_split(uint32_t P, uint32_t pix_per_view) {
+  const uint32_t v = P / pix_per_view;
+  return ViewPixel{v, P - v * pix_per_view};
+}
+
+// The pixel list of such a render: the shard's list once per view, view 0's
+// first. Work items g = lp spp + s over it keep a view's samples together,
+// so all but one wave per view boundary generate for a single view.
+inline std::vector<uint32_t> view_list(const std::vector<uint32_t>& shard, uint32_t n_views, uint32_t pix_per_view) {
+  std::vector<uint32_t> list;
+  list.reserve(shard.size() * n_views);
+  for (uint32_t v = 0; v < n_views; ++v)
+    for (uint32_t p : shard) list.push_back(view_pixel(v, p, pix_per_view));
+  return list;
 }
 
 // ---- the fork ---------------------------------------------------------------

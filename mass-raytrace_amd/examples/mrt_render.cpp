@@ -4,12 +4,20 @@
 // passes of 1 spp into the accumulation buffers, tonemap, write PNGs
 // (<out>.png, <out>_depth.png, _albedo, _normal and _denoise).
 //
-//   mrt_render <scene> <width> <height> <passes> <out.png> [asset_dir] [device]
+//   mrt_render [--orbit N] <scene> <width> <height> <passes> <out.png> [asset_dir] [device]
+//
+// --orbit N: the reference's EXPORT_FRAMES loop (main.rs:104-141) for a world
+// that does not change: N cameras on a circle around the built-in camera's
+// look_at, all rendered by ONE mrt_render_views call, each view's slice
+// tonemapped and written as frame_%05d.png next to <out.png> (which is not
+// written).
 //
 // Prints one line: scene, size, passes, render seconds, Msamples/s.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -20,9 +28,49 @@ static int fail(const char* what, mrt_ctx* ctx) {
   return 1;
 }
 
+// The built-in camera turned about the vertical axis through its look_at, in
+// n steps: Camera::new (world.rs:5-51) run backwards for what it was made
+// from (every built-in focuses on its look_at), then mrt_builder_camera.
+static bool orbit_views(mrt_builder* b, const mrt_camera& cam, uint32_t n, std::vector<mrt_view>& views) {
+  float at[3], from[3], up[3] = {0, 1, 0}, len2 = 0, vert2 = 0;
+  for (int k = 0; k < 3; ++k) {
+    at[k] = cam.lower_left_corner[k] + 0.5f * cam.horizontal[k] + 0.5f * cam.vertical[k];  // origin - focus w
+    len2 += (cam.origin[k] - at[k]) * (cam.origin[k] - at[k]);
+    vert2 += cam.vertical[k] * cam.vertical[k];
+  }
+  const float focus = std::sqrt(len2);
+  const float vfov = 2.0f * std::atan(0.5f * std::sqrt(vert2) / focus) * 180.0f / 3.14159265358979f;
+  const float hor2 = std::sqrt(cam.horizontal[0] * cam.horizontal[0] + cam.horizontal[1] * cam.horizontal[1] +
+                               cam.horizontal[2] * cam.horizontal[2]);
+  const float aspect = hor2 / std::sqrt(vert2);
+  const float dx = cam.origin[0] - at[0], dz = cam.origin[2] - at[2];
+  for (uint32_t v = 0; v < n; ++v) {
+    const float phi = 6.28318530717959f * (float)v / (float)n;
+    from[0] = at[0] + dx * std::cos(phi) + dz * std::sin(phi);
+    from[1] = cam.origin[1];
+    from[2] = at[2] - dx * std::sin(phi) + dz * std::cos(phi);
+    mrt_view view;
+    if (mrt_builder_camera(b, vfov, from, at, up, aspect, 2.0f * cam.lens_radius, focus) < 0 ||
+        mrt_builder_desc(b, nullptr, &view.camera) != MRT_OK)
+      return false;
+    view.seed = 1 + v;  // frames never share samples (main.rs:167-250: a fresh stream per render)
+    views.push_back(view);
+  }
+  return true;
+}
+
 int main(int argc, char** argv) {
+  uint32_t orbit = 0;
+  for (int i = 1; i + 1 < argc; ++i)
+    if (!std::strcmp(argv[i], "--orbit")) {
+      orbit = (uint32_t)std::atoi(argv[i + 1]);
+      for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+      argc -= 2;
+      break;
+    }
   if (argc < 6) {
-    std::fprintf(stderr, "usage: %s <scene> <width> <height> <passes> <out.png> [asset_dir] [device]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s [--orbit N] <scene> <width> <height> <passes> <out.png> [asset_dir] [device]\n",
+                 argv[0]);
     return 2;
   }
   const std::string scene = argv[1];
@@ -61,9 +109,42 @@ int main(int argc, char** argv) {
   if (mrt_upload_scene_targets(ctx, &desc, &ext, targets, n_targets) != MRT_OK)
     return fail("mrt_upload_scene_targets", ctx);
   if (mrt_set_camera(ctx, &cam) != MRT_OK) return fail("mrt_set_camera", ctx);
-  mrt_builder_free(b);
 
   const size_t n = (size_t)W * H;
+  if (orbit) {
+    std::vector<mrt_view> views;
+    if (!orbit_views(b, cam, orbit, views)) {
+      std::fprintf(stderr, "camera: %s\n", mrt_builder_last_error());
+      return 1;
+    }
+    mrt_builder_free(b);
+    std::vector<float> rgb(n * 3 * orbit, 0.0f);
+    std::vector<uint32_t> bounces(n * orbit, 0);
+    std::vector<uint8_t> bytes(n * 3);
+    const auto t0 = std::chrono::steady_clock::now();
+    mrt_render_args a{W, H, 0, passes, 0, 50, 0, 1, 0};  // the seeds are the views'
+    if (mrt_render_views(ctx, &a, views.data(), orbit, rgb.data(), bounces.data()) != MRT_OK)
+      return fail("mrt_render_views", ctx);
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    const size_t slash = out.rfind('/');
+    const std::string dir = slash == std::string::npos ? "" : out.substr(0, slash + 1);
+    for (uint32_t v = 0; v < orbit; ++v) {  // a view's slice is an ordinary W x H frame
+      if (mrt_tonemap(ctx, W, H, rgb.data() + v * n * 3, bounces.data() + v * n, passes, MRT_DISPLAY_DEFAULT,
+                      bytes.data()) != MRT_OK)
+        return fail("mrt_tonemap", ctx);
+      char name[32];
+      std::snprintf(name, sizeof name, "frame_%05u.png", v);
+      if (mrt_write_png((dir + name).c_str(), W, H, bytes.data()) != MRT_OK) {
+        std::fprintf(stderr, "png: %s\n", mrt_builder_last_error());
+        return 1;
+      }
+    }
+    std::printf("%s %ux%u views=%u passes=%u render_s=%.3f msamples_per_s=%.1f\n", scene.c_str(), W, H, orbit, passes,
+                secs, (double)n * orbit * passes / secs / 1e6);
+    mrt_destroy(ctx);
+    return 0;
+  }
+  mrt_builder_free(b);
   std::vector<float> albedo(n * 3), normal(n * 3), rgb(n * 3, 0.0f);
   std::vector<uint32_t> bounces(n, 0);
   std::vector<uint8_t> bytes(n * 3);

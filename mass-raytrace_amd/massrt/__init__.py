@@ -161,6 +161,11 @@ class MrtRenderArgs(C.Structure):
     ]
 
 
+class MrtView(C.Structure):
+    """One view of Context.render_views: a camera and the seed of its samples' streams (mrt_view)."""
+    _fields_ = [("camera", MrtCamera), ("seed", C.c_uint64)]
+
+
 class MrtHit(C.Structure):
     _fields_ = [("prim", C.c_uint32), ("container", C.c_uint32), ("t", C.c_float), ("front_face", C.c_uint32)]
 
@@ -262,6 +267,7 @@ EXPORTED_SYMBOLS = [
     "mrt_load_obj_groups",
     "mrt_upload_scene_targets", "mrt_builder_add_volume_instance", "mrt_builder_add_volume_model",
     "mrt_builder_volume_targets",
+    "mrt_render_views", "mrt_render_views_device",
 ]
 
 _lib = None
@@ -369,6 +375,8 @@ def lib() -> C.CDLL:
         "mrt_builder_add_volume_instance": (I, [P, I, fp, fp, fp, F, fp]),
         "mrt_builder_add_volume_model": (I, [P, I, F, fp]),
         "mrt_builder_volume_targets": (I, [P, C.POINTER(C.POINTER(MrtVolumeTarget)), C.POINTER(U32)]),
+        "mrt_render_views": (I, [P, C.POINTER(MrtRenderArgs), C.POINTER(MrtView), U32, fp, C.POINTER(C.c_uint32)]),
+        "mrt_render_views_device": (I, [P, C.POINTER(MrtRenderArgs), C.POINTER(MrtView), U32, P, P, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -564,6 +572,21 @@ class Builder:
         return d
 
 
+def make_camera(vfov, look_from, look_at, view_up=(0, 1, 0), aspect=float(ASPECT_RATIO), aperture=0.0,
+                focus=None) -> MrtCamera:
+    """Camera::new (world.rs:5-51) as an MrtCamera, for Context.set_camera and
+    the views of Context.render_views (a scratch Builder.camera + desc)."""
+    b = Builder(1)
+    try:
+        b.camera(vfov, look_from, look_at, view_up, aspect, aperture, focus)
+        cam = MrtCamera()
+        if lib().mrt_builder_desc(b.h, None, C.byref(cam)) != 0:  # the camera alone: the scratch world is empty
+            raise MassrtError(lib().mrt_builder_last_error().decode())
+        return cam
+    finally:
+        b.close()
+
+
 def preorder(desc: MrtSceneDesc):
     """Preorder listing of the world tree in the oracle's format:
     list of (kind, id) with kind 6 = end of node, plus boxes of nodes."""
@@ -730,6 +753,41 @@ class Context:
     def render_device(self, args: MrtRenderArgs, d_rgb: int, d_bounces: int, stream: int | None = None):
         self._check(lib().mrt_render_device(self.h, C.byref(args), C.c_void_p(d_rgb), C.c_void_p(d_bounces),
                                             C.c_void_p(stream or 0)))
+
+    @staticmethod
+    def _views(views):
+        """[(MrtCamera, seed) | MrtView, ...] -> a C array of mrt_view (None stays NULL)."""
+        if views is None:
+            return None, 0
+        vs = [v if isinstance(v, MrtView) else MrtView(v[0], int(v[1])) for v in views]
+        return (MrtView * max(len(vs), 1))(*vs), len(vs)
+
+    def render_views(self, width, height, views, spp_begin=0, spp_count=1, max_depth=MAX_DEPTH, shard_index=0,
+                     shard_count=1, flags=0, rgb=None, bounces=None):
+        """mrt_render_views: every view (MrtView, or a (MrtCamera, seed) pair) of
+        the uploaded scene in one wavefront render, view v exactly
+        set_camera(camera_v) + render(seed=seed_v). Returns (rgb float32
+        [V, H*W*3], bounces uint32 [V, H*W]); accumulates into `rgb` and
+        `bounces` when they are given. The context's camera is neither needed
+        nor changed."""
+        arr, n = self._views(views)
+        if rgb is None:
+            rgb = np.zeros((n, width * height * 3), dtype=np.float32)
+        if bounces is None:
+            bounces = np.zeros((n, width * height), dtype=np.uint32)
+        for a, dt in ((rgb, np.float32), (bounces, np.uint32)):
+            if a.dtype != dt or not a.flags.c_contiguous:
+                raise ValueError("render_views accumulates in place: contiguous float32 rgb and uint32 bounces")
+        a = self.args(width, height, spp_begin, spp_count, 0, max_depth, shard_index, shard_count, flags=flags)
+        self._check(lib().mrt_render_views(self.h, C.byref(a), arr, n, _fptr(rgb),
+                                           bounces.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return rgb, bounces
+
+    def render_views_device(self, args: MrtRenderArgs, views, d_rgb: int, d_bounces: int, stream: int | None = None):
+        """mrt_render_views_device: device buffers of V frames, view v's behind view v - 1's."""
+        arr, n = self._views(views)
+        self._check(lib().mrt_render_views_device(self.h, C.byref(args), arr, n, C.c_void_p(d_rgb),
+                                                  C.c_void_p(d_bounces), C.c_void_p(stream or 0)))
 
     def trace_rays(self, rays: np.ndarray, t_min=0.001, t_max=float("inf")):
         r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
