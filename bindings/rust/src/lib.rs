@@ -117,6 +117,26 @@ impl SceneSink {
 /// One view of `Context::render_views`: a camera and the seed of its samples' streams.
 pub type View = mrt_view;
 
+/// One path start of `Context::render_rays`: a ray, the key of its stream and the draws already taken from it.
+pub type PathRay = mrt_path_ray;
+
+/// The renderer's own camera rays of `pixels` (p = y*w + x) for `sample` as
+/// `render_rays` entries (mrt_camera_rays): key = p, skip = the draws each ray
+/// took, so `render_rays` over them with spp_begin = sample, spp_count = 1
+/// adds what `render` adds for those pixels and that sample, bit for bit.
+pub fn camera_rays(camera: &mrt_camera, w: u32, h: u32, pixels: &[u32], seed: u64, sample: u32)
+    -> Result<Vec<PathRay>, MrtError> {
+    let mut out = vec![PathRay::default(); pixels.len()];
+    let rc = unsafe {
+        mrt_camera_rays(camera, w, h, pixels.as_ptr(), pixels.len() as u32, seed, sample, out.as_mut_ptr())
+    };
+    if rc != MRT_OK {
+        let message = unsafe { CStr::from_ptr(mrt_global_last_error()) }.to_string_lossy().into_owned();
+        return Err(MrtError { code: rc, message });
+    }
+    Ok(out)
+}
+
 /// One GPU context (mrt_ctx); destroyed on drop.
 pub struct Context {
     raw: *mut mrt_ctx,
@@ -201,6 +221,20 @@ impl Context {
         assert!(rgb.len() >= 3 * n && bounces.len() >= n);
         self.check(unsafe {
             mrt_render_views(self.raw, args, views.as_ptr(), views.len() as u32, rgb.as_mut_ptr(), bounces.as_mut_ptr())
+        })
+    }
+
+    /// Whole paths for the caller's rays (mrt_render_rays): entry i, sample s
+    /// in [spp_begin, spp_begin + spp_count) is Camera::trace of that ray on
+    /// the stream of (seed, rays[i].key, s) after rays[i].skip draws, ADDED
+    /// into `rgb` (n*3) and `bounces` (n) at the entry's position i. The
+    /// context's camera is neither needed nor changed.
+    pub fn render_rays(&self, rays: &[PathRay], seed: u64, spp_begin: u32, spp_count: u32, max_depth: u32, flags: u32,
+                       rgb: &mut [f32], bounces: &mut [u32]) -> Result<(), MrtError> {
+        assert!(rgb.len() >= 3 * rays.len() && bounces.len() >= rays.len());
+        self.check(unsafe {
+            mrt_render_rays(self.raw, rays.as_ptr(), rays.len() as u32, seed, spp_begin, spp_count, max_depth, flags,
+                            rgb.as_mut_ptr(), bounces.as_mut_ptr())
         })
     }
 

@@ -277,6 +277,18 @@ pub struct mrt_view {
     pub seed: u64,
 }
 
+/// One path start of mrt_render_rays: a ray, the key of its stream and the
+/// draws already taken from that stream. 32 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct mrt_path_ray {
+    pub origin: [f32; 3],
+    pub direction: [f32; 3],
+    pub key: u32,
+    pub skip: u32,
+}
+pub const MRT_RAY_SKIP_MAX: u32 = 4096;
+
 #[repr(C)]
 #[derive(Clone, Copy, Default, Debug)]
 pub struct mrt_hit {
@@ -415,6 +427,15 @@ extern "C" {
     pub fn mrt_render_views_device(ctx: *mut mrt_ctx, args: *const mrt_render_args, views: *const mrt_view,
                                    n_views: u32, d_accum_rgb: *mut f32, d_accum_bounces: *mut u32,
                                    hip_stream: *mut c_void) -> i32;
+    pub fn mrt_render_rays(ctx: *mut mrt_ctx, rays: *const mrt_path_ray, n_rays: u32, seed: u64, spp_begin: u32,
+                           spp_count: u32, max_depth: u32, flags: u32, accum_rgb: *mut f32, accum_bounces: *mut u32)
+        -> i32;
+    pub fn mrt_render_rays_device(ctx: *mut mrt_ctx, d_rays: *const mrt_path_ray, n_rays: u32, seed: u64,
+                                  spp_begin: u32, spp_count: u32, max_depth: u32, flags: u32, d_accum_rgb: *mut f32,
+                                  d_accum_bounces: *mut u32, hip_stream: *mut c_void) -> i32;
+    pub fn mrt_path_stream(seed: u64, key: u32, sample: u32, n: u32, out_u64: *mut u64, out_f32: *mut f32) -> i32;
+    pub fn mrt_camera_rays(camera: *const mrt_camera, width: u32, height: u32, pixels: *const u32, n: u32, seed: u64,
+                           sample: u32, out: *mut mrt_path_ray) -> i32;
     pub fn mrt_trace_rays(ctx: *mut mrt_ctx, rays: *const f32, n: u32, t_min: f32, t_max: f32, out: *mut mrt_hit)
         -> i32;
     pub fn mrt_get_counters(ctx: *mut mrt_ctx, out: *mut mrt_counters) -> i32;

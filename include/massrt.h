@@ -271,6 +271,16 @@ typedef struct {
   uint64_t seed;
 } mrt_view;
 
+/* One path start of mrt_render_rays:
+ * Camera::trace(world, Ray::new(origin, direction), max_depth) (world.rs:65-79). 32 B. */
+typedef struct {
+  float origin[3];
+  float direction[3];
+  uint32_t key;  /* stream key, in the place of the pixel index */
+  uint32_t skip; /* draws already taken from that stream by whoever built the ray */
+} mrt_path_ray;
+#define MRT_RAY_SKIP_MAX 4096u
+
 /* Closest hit of one ray (parity entry point). */
 typedef struct {
   uint32_t prim;      /* MRT_REF(kind, index) of the primitive hit, or NONE */
@@ -397,6 +407,60 @@ int mrt_render_views(mrt_ctx* ctx, const mrt_render_args* args, const mrt_view* 
                      float* accum_rgb, uint32_t* accum_bounces);
 int mrt_render_views_device(mrt_ctx* ctx, const mrt_render_args* args, const mrt_view* views, uint32_t n_views,
                             float* d_accum_rgb, uint32_t* d_accum_bounces, void* hip_stream);
+/* Whole paths for rays the caller chose (another camera model: orthographic,
+ * fisheye, equirectangular, a calibrated lens; light and irradiance probes;
+ * per-ray supervision of a learned model). Entry i with sample s in
+ * [spp_begin, spp_begin + spp_count) is one path: Camera::trace (world.rs:65-79)
+ * of that fixed ray to max_depth, through the same wavefront loop as a frame.
+ * Its results are ADDED in sample order, exactly as mrt_render adds a pixel's:
+ *   accum_rgb[3*i+c] += color_c, accum_bounces[i] += max_depth - depth
+ * The result index is the entry's position i, never its key.
+ *  - Streams: the path of entry i, sample s draws from the stream of
+ *    (seed, rays[i].key, s), after rays[i].skip draws (the generation kernel
+ *    calls next() skip times before the first traversal). So one call with
+ *    spp_count = k gives the bits of k calls of one sample each, a permuted
+ *    list gives the same bits permuted, and equal entries give equal results.
+ *    Entries that share (key, sample) but differ in their ray share random
+ *    numbers: choosing the keys is the caller's business.
+ *  - Camera equivalence: mrt_camera_rays writes, for pixel p = y*width + x
+ *    (pixels[j], j < n) and sample `sample`, the ray that the renderer's own
+ *    thin-lens camera builds from the stream of (seed, p, sample) — main.rs:
+ *    258-260 plus Camera::ray, world.rs:53-63, in IEEE f32, in that order of
+ *    operations, uncontracted — with key = p and skip = the draws that ray
+ *    took (2 for the jitter, 2 per try of random_in_unit_disk).
+ *    mrt_render_rays over those entries with spp_begin = sample, spp_count = 1
+ *    then adds per entry exactly what mrt_render adds for that pixel and
+ *    sample, bit for bit. Host only, no context; MRT_ERR_INVALID: a null
+ *    camera, pixels or out with n > 0, width*height == 0 or >= 2^32, a pixel
+ *    >= width*height. n == 0 writes nothing.
+ *  - mrt_path_stream publishes the stream: n raw outputs of the stream of
+ *    (seed, key, sample) into out_u64 and their f32 mapping (fastrand's, on the
+ *    high 32 bits) into out_f32; either may be NULL. Host only, no context.
+ *  - Before anything is enqueued: rays == NULL, n_rays == 0, MRT_RENDER_FUSED
+ *    or MRT_RENDER_SIMPLE_TRACE (one camera each), spp_begin + spp_count >
+ *    2^32 - 1 or a null accumulation buffer is MRT_ERR_INVALID, as is (host
+ *    form only) a skip above MRT_RAY_SKIP_MAX; no scene uploaded is
+ *    MRT_ERR_STATE; buffers that do not fit the device are MRT_ERR_NOMEM as
+ *    for mrt_render. The _device form cannot inspect its table: its kernel
+ *    draws min(skip, MRT_RAY_SKIP_MAX). Ray values are not validated: any
+ *    bits are allowed, as for mrt_trace_rays. spp_count == 0 or max_depth == 0
+ *    adds nothing and returns MRT_OK. MRT_RENDER_COUNTERS and
+ *    MRT_RENDER_TIME_KERNELS work as for a frame.
+ *  - The call neither needs nor changes the context's camera. On a
+ *    multi-device context it runs on device 0. The _device form is ordered on
+ *    `hip_stream` and does not wait; d_rays (device memory, 16-byte aligned)
+ *    must stay unchanged until the work on that stream has ended. The host
+ *    form copies the table into a buffer the context owns and returns when the
+ *    sums are back. */
+int mrt_render_rays(mrt_ctx* ctx, const mrt_path_ray* rays, uint32_t n_rays, uint64_t seed, uint32_t spp_begin,
+                    uint32_t spp_count, uint32_t max_depth, uint32_t flags, float* accum_rgb,
+                    uint32_t* accum_bounces);
+int mrt_render_rays_device(mrt_ctx* ctx, const mrt_path_ray* d_rays, uint32_t n_rays, uint64_t seed,
+                           uint32_t spp_begin, uint32_t spp_count, uint32_t max_depth, uint32_t flags,
+                           float* d_accum_rgb, uint32_t* d_accum_bounces, void* hip_stream);
+int mrt_path_stream(uint64_t seed, uint32_t key, uint32_t sample, uint32_t n, uint64_t* out_u64, float* out_f32);
+int mrt_camera_rays(const mrt_camera* camera, uint32_t width, uint32_t height, const uint32_t* pixels, uint32_t n,
+                    uint64_t seed, uint32_t sample, mrt_path_ray* out);
 /* rays: n x {ox,oy,oz,dx,dy,dz} host floats; out: n hits. Draws during the
  * traversal (Volume, Mix alpha tests) use ray i's stream keyed
  * (seed 0, i, sample 0xFFFFFFFE). */

@@ -110,6 +110,8 @@ int mrt_create(int device, mrt_ctx** out) {
     HIP_CHECK(hipMemset(c->work.p, 0, 256));
     HIP_CHECK(hipEventCreateWithFlags(&c->acc_done, hipEventDisableTiming));
     HIP_CHECK(hipEventCreateWithFlags(&c->set_fork, hipEventDisableTiming));
+    HIP_CHECK(hipEventCreateWithFlags(&c->rays_ready, hipEventDisableTiming));
+    HIP_CHECK(hipEventCreateWithFlags(&c->ids_ready, hipEventDisableTiming));
     HIP_CHECK(c->d_cnt.alloc(1));
     HIP_CHECK(hipMemset(c->d_cnt.p, 0, sizeof(DevCounters)));
     HIP_CHECK(c->dbg.alloc(4));
@@ -149,6 +151,8 @@ int mrt_destroy(mrt_ctx* c) {
     if (q.stream) hipStreamSynchronize(q.stream);
   if (c->acc_done) hipEventDestroy(c->acc_done);
   if (c->set_fork) hipEventDestroy(c->set_fork);
+  if (c->rays_ready) hipEventDestroy(c->rays_ready);
+  if (c->ids_ready) hipEventDestroy(c->ids_ready);
   for (Queue& q : c->q) {
     if (q.h_stat) hipHostFree(q.h_stat);
     for (hipEvent_t e : {q.ev[0], q.ev[1], q.join})

@@ -110,6 +110,13 @@ struct mrt_ctx {
   std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t>, DevBuf<uint32_t>> pixlists;
   DevBuf<DevView> views;  // the view table of the last mrt_render_views (grown on demand; the kernels only read it)
   std::vector<DevView> views_h;  // its host copy, the upload's source
+  // mrt_render_rays: the identity list its accumulate takes (grown on demand, filled once on the stream of the call
+  // that grew it: ids_ready, which every call's stream waits for), the host form's copy of the caller's table, and
+  // the event that orders the queues after the caller's stream, the table's writer
+  DevBuf<uint32_t> ray_ids;
+  hipEvent_t ids_ready = nullptr;
+  DevBuf<mrt_path_ray> rays_d;
+  hipEvent_t rays_ready = nullptr;
   // host-buffer render staging
   DevBuf<float> d_acc_rgb;
   DevBuf<uint32_t> d_acc_b;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include "../host/loop.h"
 #include "path.h"
 
 constexpr int kBlock = 256;
@@ -87,6 +88,19 @@ struct ViewTable {
   uint32_t n_views;
   uint32_t* dbg;  // MRT_IDX's record (DevScene::dbg)
 };
+
+// Where the ray variants of the generation kernels take a path's start from
+// (mrt_render_rays): work item g = i spp + s is sample s of entry i (loop.h
+// ray_work), its result goes to list position i. Entries are 32 B, read as two
+// 16-byte loads: the table is 16-byte aligned. The kernels only read it.
+struct RayTable {
+  const mrt_path_ray* rays;
+  uint32_t n;
+  uint32_t* dbg;  // MRT_IDX's record (DevScene::dbg)
+};
+static_assert(sizeof(mrt_path_ray) == 32 && offsetof(mrt_path_ray, key) == 24 && offsetof(mrt_path_ray, skip) == 28,
+              "mrt_path_ray: two quads, {o, d.x} {d.y, d.z, key, skip}");
+static_assert(mrt::kRaySkipMax == MRT_RAY_SKIP_MAX, "loop.h ray_skip clamps to the ABI's limit");
 
 constexpr float kTmin = 0.001f;         // World::intersect(ray, 0.001, INFINITY) (main.rs trace)
 constexpr uint32_t kIdle = 0xFFFFFFFFu;  // Trav.ray of a lane without a ray

@@ -30,7 +30,8 @@ namespace {
 constexpr int kShadeBlock = MRT_SHADE_BLOCK;
 
 // Where a work item's camera comes from (CAM): the render's one camera, by
-// value in the kernel's arguments, or a table of views (mrt_render_views).
+// value in the kernel's arguments, or a table of views (mrt_render_views); a
+// table of rays (mrt_render_rays) has its own gen_work below.
 // work_camera gives the camera and the stream seed of pixel-list entry p and
 // leaves in p the pixel within its frame.
 __device__ __forceinline__ const DevCamera& work_camera(const DevCamera& cam, const RenderParams& rp, uint32_t& p,
@@ -71,6 +72,25 @@ __device__ __forceinline__ void gen_work(const CAM& cam, const RenderParams& rp,
   rs = rng_pack(rng);
 }
 
+// A third source (mrt_render_rays): the path's start comes from a table of
+// rays instead of a camera. Work item g is sample s of entry i (loop.h
+// ray_work); the lane loads its 32-B entry as two quads (consecutive entries:
+// a wave reads at most 2 KiB contiguous), takes the stream of (seed, key,
+// sample) and advances it by the entry's skip, the draws whoever built the ray
+// already took. The record is a camera path's: ro.w the work item, rd.w 0
+// bounces. No pixel list is read: the result index is the list position.
+__device__ __forceinline__ void gen_work(const RayTable& t, const RenderParams& rp, uint32_t g, float4& ro, float4& rd,
+                                         uint4& rs) {
+  const RayWork w = ray_work(g, rp.spp);
+  const uint4* e = reinterpret_cast<const uint4*>(t.rays + MRT_IDX(t, w.i, t.n, 27));
+  const uint4 a = e[0], b = e[1];  // {o.x, o.y, o.z, d.x} {d.y, d.z, key, skip}
+  PathRng rng = path_rng(rp.seed, b.z, rp.sample_base + w.s);
+  for (uint32_t k = ray_skip(b.w); k != 0; --k) rng.next();
+  ro = make_float4(__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z), __uint_as_float(g));
+  rd = make_float4(__uint_as_float(a.w), __uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(0u));
+  rs = rng_pack(rng);
+}
+
 // The new camera path of work item g into slot i of a pool.
 template <typename CAM>
 __device__ __forceinline__ void gen_path(const CAM& cam, const RenderParams& rp, const PathBufs& out, uint32_t g,
@@ -96,6 +116,19 @@ __global__ __launch_bounds__(kBlock) void k_generate_views(ViewTable views, Rend
   uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n0) return;
   gen_path(views, rp, out, base + i, i);
+}
+__global__ __launch_bounds__(kBlock) void k_generate_rays(RayTable rays, RenderParams rp, PathBufs out, uint32_t base,
+                                                          uint32_t n0) {
+  uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n0) return;
+  gen_path(rays, rp, out, base + i, i);
+}
+
+// The identity list of a ray list's render: k_accumulate adds list entry i's
+// samples to accum[list[i]], and entry i of a ray list is its own result index.
+__global__ __launch_bounds__(kBlock) void k_identity(uint32_t* list, uint32_t n) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) list[i] = i;
 }
 
 // Lagged status read of a queue (host loop, one per batch): the fields the
@@ -165,6 +198,10 @@ __global__ __launch_bounds__(kBlock) void k_refill(DevCamera cam, RenderParams r
 __global__ __launch_bounds__(kBlock) void k_refill_views(ViewTable views, RenderParams rp, PathBufs out,
                                                          const Ctrl* ctrl) {
   refill(views, rp, out, ctrl);
+}
+__global__ __launch_bounds__(kBlock) void k_refill_rays(RayTable rays, RenderParams rp, PathBufs out,
+                                                        const Ctrl* ctrl) {
+  refill(rays, rp, out, ctrl);
 }
 
 // k_shade only shades and compacts: new camera rays go in behind the
@@ -656,6 +693,7 @@ struct Pass {
   uint32_t finish_paths;  // drain hand-off threshold (0: never)
   ShadeFn shade;
   ViewTable views;  // views.views != nullptr: a batch of views, the cameras from this table (the context's otherwise)
+  RayTable rays;    // rays.rays != nullptr: a caller's ray list, the path starts from this table (no camera at all)
 };
 
 // The argument and state errors of a render, before anything is enqueued.
@@ -703,7 +741,9 @@ void fork_queues(mrt_ctx* c, const RenderParams& rp, const Pass& p) {
     HIP_CHECK(hipMemcpyAsync(q.ctrl.p, &init, sizeof(Ctrl), hipMemcpyHostToDevice, q.stream));
     if (nk) {
       const dim3 grid((nk + kBlock - 1) / kBlock);
-      if (p.views.views)
+      if (p.rays.rays)
+        hipLaunchKernelGGL(k_generate_rays, grid, dim3(kBlock), 0, q.stream, p.rays, rp, q.bufs[0], base, nk);
+      else if (p.views.views)
         hipLaunchKernelGGL(k_generate_views, grid, dim3(kBlock), 0, q.stream, p.views, rp, q.bufs[0], base, nk);
       else
         hipLaunchKernelGGL(k_generate, grid, dim3(kBlock), 0, q.stream, c->cam, rp, q.bufs[0], base, nk);
@@ -729,7 +769,10 @@ void enqueue_batch(mrt_ctx* c, Queue& q, QueueLoop& L, const RenderParams& rp, c
     HIP_CHECK(hipGetLastError());
     if (!L.exhausted || rp.shade_bin == 2) {  // new paths behind the survivors (shade_bin 2: and the pool's ends joined)
       hipLaunchKernelGGL(k_reserve, dim3(1), dim3(64), 0, q.stream, q.ctrl.p, cur, c->work.p, rp.G, rp.pool_cap);
-      if (p.views.views)
+      if (p.rays.rays)
+        hipLaunchKernelGGL(k_refill_rays, dim3(c->refill_grid), dim3(kBlock), 0, q.stream, p.rays, rp,
+                           q.bufs[cur ^ 1], (const Ctrl*)q.ctrl.p);
+      else if (p.views.views)
         hipLaunchKernelGGL(k_refill_views, dim3(c->refill_grid), dim3(kBlock), 0, q.stream, p.views, rp,
                            q.bufs[cur ^ 1], (const Ctrl*)q.ctrl.p);
       else
@@ -807,10 +850,16 @@ void join_queues(mrt_ctx* c, hipStream_t st) {
 namespace {
 
 // The wavefront loop over a pixel list, every step from plan_buffers on: what
-// a render of the context's camera and a render of a batch of views
-// (views.views != nullptr; the list then holds global pixels) share.
+// a render of the context's camera, a render of a batch of views
+// (views.views != nullptr; the list then holds global pixels) and a render of
+// a caller's ray list (rays.rays != nullptr; the list is the identity, width
+// and height are not read) share.
+// The drain hand-off needs no camera under either table: launch_finish's
+// kernel only adopts live paths (ADOPT: gen_work is not in it), so the
+// context's camera, set or not, is passed and never read.
 void render_wavefront(mrt_ctx* c, const mrt_render_args* a, const uint32_t* pixlist_d, uint32_t n_pix,
-                      uint32_t spp_chunk, const ViewTable& views, float* d_rgb, uint32_t* d_b, hipStream_t st) {
+                      uint32_t spp_chunk, const ViewTable& views, const RayTable& rays, float* d_rgb, uint32_t* d_b,
+                      hipStream_t st) {
   const bool count = (a->flags & MRT_RENDER_COUNTERS) != 0;
   const bool simple = (a->flags & MRT_RENDER_SIMPLE_TRACE) != 0;
   plan_buffers(c, n_pix, spp_chunk, true);
@@ -821,7 +870,7 @@ void render_wavefront(mrt_ctx* c, const mrt_render_args* a, const uint32_t* pixl
   // any queue runs (ensure_slots reallocates)
   const bool can_finish = !c->facts.trav_rng && !c->scene_ext && !simple;
   const Pass p{count, simple, can_finish ? c->tun.finish_paths : 0u, shade_kernel(count, c->scene_ext, c->tun.shade_wpe),
-               views};
+               views, rays};
   if (p.finish_paths) ensure_slots(c, (size_t)finish_grid(c, count) * kBlock * kMaxQueues);
   for (uint32_t done = 0; done < a->spp_count; done += spp_chunk) {
     const uint32_t cs = std::min(spp_chunk, a->spp_count - done);
@@ -851,7 +900,7 @@ void render_device(mrt_ctx* c, const mrt_render_args* a, float* d_rgb, uint32_t*
     render_fused(c, a, pl.first, n_pix, spp_chunk, d_rgb, d_b, st);
     return;
   }
-  render_wavefront(c, a, pl.first, n_pix, spp_chunk, ViewTable{}, d_rgb, d_b, st);
+  render_wavefront(c, a, pl.first, n_pix, spp_chunk, ViewTable{}, RayTable{}, d_rgb, d_b, st);
 }
 
 // mrt_render_views_device: one wavefront render over the shard's pixels of
@@ -891,7 +940,52 @@ void render_views_device(mrt_ctx* c, const mrt_render_args* a, const mrt_view* v
   HIP_CHECK(hipMemcpyAsync(c->views.p, table.data(), (size_t)n_views * sizeof(DevView), hipMemcpyHostToDevice,
                            c->q[0].stream));
   const ViewTable vt{c->views.p, a->width * a->height, n_views, c->dbg.p};
-  render_wavefront(c, a, pl.first, n_pix, first_chunk(a->spp_count, c->tun.results_max, n_pix), vt, d_rgb, d_b, st);
+  render_wavefront(c, a, pl.first, n_pix, first_chunk(a->spp_count, c->tun.results_max, n_pix), vt, RayTable{}, d_rgb,
+                   d_b, st);
+}
+
+// The argument and state errors of a ray list's render, before anything is
+// enqueued; `host`: the table is in host memory and its skips can be read.
+static void check_rays_args(const mrt_ctx* c, const mrt_path_ray* rays, uint32_t n_rays, uint32_t spp_begin,
+                     uint32_t spp_count, uint32_t flags, const void* rgb, const void* bounces, bool host) {
+  if (!rgb || !bounces) throw ApiError{MRT_ERR_INVALID, "null accumulation buffer"};
+  if (!rays || n_rays == 0) throw ApiError{MRT_ERR_INVALID, "mrt_render_rays: no rays"};
+  if (flags & (MRT_RENDER_FUSED | MRT_RENDER_SIMPLE_TRACE))
+    throw ApiError{MRT_ERR_INVALID, "mrt_render_rays: MRT_RENDER_FUSED and MRT_RENDER_SIMPLE_TRACE render one camera"};
+  if (!samples_fit(spp_begin, spp_count)) throw ApiError{MRT_ERR_INVALID, "sample index overflow"};
+  if (host) {
+    const uint32_t bad = first_bad_skip(rays, n_rays);
+    if (bad < n_rays)
+      throw ApiError{MRT_ERR_INVALID, "mrt_render_rays: entry " + std::to_string(bad) + " has skip " +
+                                          std::to_string(rays[bad].skip) + ", above MRT_RAY_SKIP_MAX"};
+  }
+  if (!c->has_scene) throw ApiError{MRT_ERR_STATE, "no scene uploaded"};
+}
+
+// mrt_render_rays_device: one wavefront render over the work items of a ray
+// list on the device (loop.h ray_work), every step a frame's from plan_buffers
+// on. The queues' generation kernels read the table, which the caller's
+// stream may have just written: queue 0's stream, on which every fork of this
+// render follows, waits for `st` as it stands now.
+static void render_rays_device(mrt_ctx* c, const mrt_path_ray* d_rays, uint32_t n_rays, uint64_t seed, uint32_t spp_begin,
+                        uint32_t spp_count, uint32_t max_depth, uint32_t flags, float* d_rgb, uint32_t* d_b,
+                        hipStream_t st) {
+  if ((uintptr_t)d_rays & 15u) throw ApiError{MRT_ERR_INVALID, "mrt_render_rays: the device table must be 16-byte aligned"};
+  if (spp_count == 0 || max_depth == 0) return;  // trace(ray, 0) returns (0, 0) for every sample: nothing to add
+  if (c->ray_ids.n < n_rays) {
+    if (c->ray_ids.p) HIP_CHECK(hipDeviceSynchronize());  // an earlier render's accumulate may still read the old list
+    HIP_CHECK(c->ray_ids.alloc(n_rays));
+    hipLaunchKernelGGL(k_identity, dim3((n_rays + kBlock - 1) / kBlock), dim3(kBlock), 0, st, c->ray_ids.p, n_rays);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(c->ids_ready, st));
+  }
+  HIP_CHECK(hipStreamWaitEvent(st, c->ids_ready, 0));  // the list's one fill, whatever stream it ran on
+  HIP_CHECK(hipEventRecord(c->rays_ready, st));
+  HIP_CHECK(hipStreamWaitEvent(c->q[0].stream, c->rays_ready, 0));
+  const mrt_render_args a{n_rays, 1u, spp_begin, spp_count, seed, max_depth, 0u, 1u, flags};
+  const RayTable rt{d_rays, n_rays, c->dbg.p};
+  render_wavefront(c, &a, c->ray_ids.p, n_rays, first_chunk(spp_count, c->tun.results_max, n_rays), ViewTable{}, rt,
+                   d_rgb, d_b, st);
 }
 
 // Kernel timing of renders flagged MRT_RENDER_TIME_KERNELS, resolved when the
@@ -976,6 +1070,42 @@ int mrt_render_views(mrt_ctx* c, const mrt_render_args* a, const mrt_view* views
     render_views_device(c, a, views, n_views, d_rgb, d_b, c->stream);
     HIP_CHECK(hipMemcpyAsync(rgb, d_rgb, np * 12, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipMemcpyAsync(bounces, d_b, np * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+  });
+}
+
+int mrt_render_rays_device(mrt_ctx* c, const mrt_path_ray* d_rays, uint32_t n_rays, uint64_t seed, uint32_t spp_begin,
+                           uint32_t spp_count, uint32_t max_depth, uint32_t flags, float* d_rgb, uint32_t* d_b,
+                           void* stream) {
+  MRT_DEV0(c, mrt_render_rays_device(c, d_rays, n_rays, seed, spp_begin, spp_count, max_depth, flags, d_rgb, d_b,
+                                     stream));
+  return guarded(c, [&] {
+    check_rays_args(c, d_rays, n_rays, spp_begin, spp_count, flags, d_rgb, d_b, false);
+    render_rays_device(c, d_rays, n_rays, seed, spp_begin, spp_count, max_depth, flags, d_rgb, d_b,
+                       (hipStream_t)stream);  // NULL: the null stream
+  });
+}
+
+int mrt_render_rays(mrt_ctx* c, const mrt_path_ray* rays, uint32_t n_rays, uint64_t seed, uint32_t spp_begin,
+                    uint32_t spp_count, uint32_t max_depth, uint32_t flags, float* rgb, uint32_t* bounces) {
+  MRT_DEV0(c, mrt_render_rays(c, rays, n_rays, seed, spp_begin, spp_count, max_depth, flags, rgb, bounces));
+  return guarded(c, [&] {
+    check_rays_args(c, rays, n_rays, spp_begin, spp_count, flags, rgb, bounces, true);
+    if (spp_count == 0 || max_depth == 0) return;  // nothing to add: the buffers stay as they are
+    const size_t n = n_rays;
+    // the table goes into the context's own buffer; the last host-form call's
+    // kernels, its only readers, ended before that call returned
+    HIP_CHECK(c->rays_d.reserve(n));
+    HIP_CHECK(c->d_acc_rgb.reserve(n * 3));
+    HIP_CHECK(c->d_acc_b.reserve(n));
+    float* d_rgb = c->d_acc_rgb.p;
+    uint32_t* d_b = c->d_acc_b.p;
+    HIP_CHECK(hipMemcpyAsync(c->rays_d.p, rays, n * sizeof(mrt_path_ray), hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(hipMemcpyAsync(d_rgb, rgb, n * 12, hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(hipMemcpyAsync(d_b, bounces, n * 4, hipMemcpyHostToDevice, c->stream));
+    render_rays_device(c, c->rays_d.p, n_rays, seed, spp_begin, spp_count, max_depth, flags, d_rgb, d_b, c->stream);
+    HIP_CHECK(hipMemcpyAsync(rgb, d_rgb, n * 12, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipMemcpyAsync(bounces, d_b, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_CHECK(hipStreamSynchronize(c->stream));
   });
 }

@@ -1,10 +1,12 @@
 // loop.h — the integer decisions of the wavefront loop (render.hip): the
 // refill and gap-closing plan of k_reserve, the sizes of the path pool and
 // the results slab, the pixel lists of a shard and of a batch of views, the
-// split of a chunk's first paths over the queues, and what a queue does with
-// a lagged status read. Plain C++, no HIP: every function here runs on the
-// host in tools/loop_check.cpp (tests/test_loop.py) or tools/views_check.cpp
-// (tests/test_views.py); those a kernel also calls carry MRT_HD.
+// work items and limits of a caller's ray list, the split of a chunk's first
+// paths over the queues, and what a queue does with a lagged status read.
+// Plain C++, no HIP: every function here runs on the host in
+// tools/loop_check.cpp (tests/test_loop.py), tools/views_check.cpp
+// (tests/test_views.py) or tools/rays_check.cpp (tests/test_rays.py); those a
+// kernel also calls carry MRT_HD.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -147,6 +149,40 @@ inline std::vector<uint32_t> view_list(const std::vector<uint32_t>& shard, uint3
   for (uint32_t v = 0; v < n_views; ++v)
     for (uint32_t p : shard) list.push_back(view_pixel(v, p, pix_per_view));
   return list;
+}
+
+// ---- ray lists (mrt_render_rays) --------------------------------------------
+
+// A render of a caller's ray list runs over work items g = i spp + s: sample s
+// of the chunk for entry i, sample-minor as a frame's (g = pixel spp + sample),
+// so the results slab and k_accumulate see entry i where they see list pixel
+// i, and the list k_accumulate takes is the identity.
+struct RayWork {
+  uint32_t i, s;
+};
+MRT_HD RayWork ray_work(uint32_t g, uint32_t spp) {
+  const uint32_t i = g / spp;
+  return RayWork{i, g - i * spp};
+}
+
+// Draws an entry's stream is advanced by before its path starts: its skip,
+// at most kRaySkipMax (MRT_RAY_SKIP_MAX; the host form refuses more, the
+// device form cannot look and clamps).
+constexpr uint32_t kRaySkipMax = 4096u;
+MRT_HD uint32_t ray_skip(uint32_t skip) { return skip < kRaySkipMax ? skip : kRaySkipMax; }
+
+// The first entry of a host table whose skip is above the limit; n: none.
+template <typename RAY>
+inline uint32_t first_bad_skip(const RAY* rays, uint32_t n) {
+  for (uint32_t i = 0; i < n; ++i)
+    if (rays[i].skip > kRaySkipMax) return i;
+  return n;
+}
+
+// Samples [spp_begin, spp_begin + spp_count): the end fits 32 bits, the limit
+// a frame's render has.
+inline bool samples_fit(uint32_t spp_begin, uint32_t spp_count) {
+  return (uint64_t)spp_begin + spp_count <= 0xFFFFFFFFull;
 }
 
 // ---- the fork ---------------------------------------------------------------

@@ -12,6 +12,13 @@
 // tonemapped and written as frame_%05d.png next to <out.png> (which is not
 // written).
 //
+// --pano W H: a camera model the library does not have, through
+// mrt_render_rays: an equirectangular 360-degree frame of W x H pixels from the
+// built-in camera's look_from, written to <out.png> (the <width> <height> of
+// the command line are not used). The rays are built here on the host, one
+// per pixel through its centre, key = the pixel, skip = 0; host buffers, then
+// mrt_tonemap and mrt_write_png.
+//
 // Prints one line: scene, size, passes, render seconds, Msamples/s.
 #include <chrono>
 #include <cmath>
@@ -59,17 +66,44 @@ static bool orbit_views(mrt_builder* b, const mrt_camera& cam, uint32_t n, std::
   return true;
 }
 
+// One ray per pixel of a W x H equirectangular frame around `from`: column x
+// is the longitude (the frame's centre looks down -z, x grows to the right),
+// row y the latitude, y = 0 the bottom row as in every accumulation buffer.
+static std::vector<mrt_path_ray> pano_rays(const float* from, uint32_t W, uint32_t H) {
+  std::vector<mrt_path_ray> rays((size_t)W * H);
+  for (uint32_t y = 0; y < H; ++y)
+    for (uint32_t x = 0; x < W; ++x) {
+      const float lon = (((float)x + 0.5f) / (float)W - 0.5f) * 6.28318530717959f;
+      const float lat = (((float)y + 0.5f) / (float)H - 0.5f) * 3.14159265358979f;
+      mrt_path_ray& r = rays[(size_t)y * W + x];
+      for (int k = 0; k < 3; ++k) r.origin[k] = from[k];
+      r.direction[0] = std::cos(lat) * std::sin(lon);
+      r.direction[1] = std::sin(lat);
+      r.direction[2] = -std::cos(lat) * std::cos(lon);
+      r.key = y * W + x;  // the pixel's own stream, as a frame's pixel has
+      r.skip = 0;         // no draw went into the ray
+    }
+  return rays;
+}
+
 int main(int argc, char** argv) {
-  uint32_t orbit = 0;
+  uint32_t orbit = 0, pano_w = 0, pano_h = 0;
   for (int i = 1; i + 1 < argc; ++i)
     if (!std::strcmp(argv[i], "--orbit")) {
       orbit = (uint32_t)std::atoi(argv[i + 1]);
       for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
       argc -= 2;
       break;
+    } else if (!std::strcmp(argv[i], "--pano") && i + 2 < argc) {
+      pano_w = (uint32_t)std::atoi(argv[i + 1]);
+      pano_h = (uint32_t)std::atoi(argv[i + 2]);
+      for (int j = i; j + 3 < argc; ++j) argv[j] = argv[j + 3];
+      argc -= 3;
+      break;
     }
   if (argc < 6) {
-    std::fprintf(stderr, "usage: %s [--orbit N] <scene> <width> <height> <passes> <out.png> [asset_dir] [device]\n",
+    std::fprintf(stderr,
+                 "usage: %s [--orbit N | --pano W H] <scene> <width> <height> <passes> <out.png> [asset_dir] [device]\n",
                  argv[0]);
     return 2;
   }
@@ -110,6 +144,29 @@ int main(int argc, char** argv) {
     return fail("mrt_upload_scene_targets", ctx);
   if (mrt_set_camera(ctx, &cam) != MRT_OK) return fail("mrt_set_camera", ctx);
 
+  if (pano_w && pano_h) {
+    mrt_builder_free(b);
+    const std::vector<mrt_path_ray> rays = pano_rays(cam.origin, pano_w, pano_h);  // lens_radius 0: origin = look_from
+    std::vector<float> rgb(rays.size() * 3, 0.0f);
+    std::vector<uint32_t> bounces(rays.size(), 0);
+    std::vector<uint8_t> bytes(rays.size() * 3);
+    const auto t0 = std::chrono::steady_clock::now();
+    if (mrt_render_rays(ctx, rays.data(), (uint32_t)rays.size(), 1, 0, passes, 50, 0, rgb.data(), bounces.data()) !=
+        MRT_OK)
+      return fail("mrt_render_rays", ctx);
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    // entry y*W + x is pixel (x, y) of an ordinary W x H frame
+    if (mrt_tonemap(ctx, pano_w, pano_h, rgb.data(), bounces.data(), passes, MRT_DISPLAY_DEFAULT, bytes.data()) != MRT_OK)
+      return fail("mrt_tonemap", ctx);
+    if (mrt_write_png(out.c_str(), pano_w, pano_h, bytes.data()) != MRT_OK) {
+      std::fprintf(stderr, "png: %s\n", mrt_builder_last_error());
+      return 1;
+    }
+    std::printf("%s pano %ux%u passes=%u render_s=%.3f msamples_per_s=%.1f\n", scene.c_str(), pano_w, pano_h, passes,
+                secs, (double)rays.size() * passes / secs / 1e6);
+    mrt_destroy(ctx);
+    return 0;
+  }
   const size_t n = (size_t)W * H;
   if (orbit) {
     std::vector<mrt_view> views;

@@ -166,6 +166,19 @@ class MrtView(C.Structure):
     _fields_ = [("camera", MrtCamera), ("seed", C.c_uint64)]
 
 
+RAY_SKIP_MAX = 4096  # MRT_RAY_SKIP_MAX
+
+
+class MrtPathRay(C.Structure):
+    """One path start of Context.render_rays: a ray, the key of its stream and
+    the draws already taken from it (mrt_path_ray, 32 B)."""
+    _fields_ = [("origin", C.c_float * 3), ("direction", C.c_float * 3), ("key", C.c_uint32), ("skip", C.c_uint32)]
+
+
+# mrt_path_ray as a numpy record: what render_rays takes and camera_rays returns
+PATH_RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("key", "<u4"), ("skip", "<u4")])
+
+
 class MrtHit(C.Structure):
     _fields_ = [("prim", C.c_uint32), ("container", C.c_uint32), ("t", C.c_float), ("front_face", C.c_uint32)]
 
@@ -268,6 +281,7 @@ EXPORTED_SYMBOLS = [
     "mrt_upload_scene_targets", "mrt_builder_add_volume_instance", "mrt_builder_add_volume_model",
     "mrt_builder_volume_targets",
     "mrt_render_views", "mrt_render_views_device",
+    "mrt_render_rays", "mrt_render_rays_device", "mrt_path_stream", "mrt_camera_rays",
 ]
 
 _lib = None
@@ -377,6 +391,11 @@ def lib() -> C.CDLL:
         "mrt_builder_volume_targets": (I, [P, C.POINTER(C.POINTER(MrtVolumeTarget)), C.POINTER(U32)]),
         "mrt_render_views": (I, [P, C.POINTER(MrtRenderArgs), C.POINTER(MrtView), U32, fp, C.POINTER(C.c_uint32)]),
         "mrt_render_views_device": (I, [P, C.POINTER(MrtRenderArgs), C.POINTER(MrtView), U32, P, P, P]),
+        "mrt_render_rays": (I, [P, C.POINTER(MrtPathRay), U32, U64, U32, U32, U32, U32, fp, C.POINTER(C.c_uint32)]),
+        "mrt_render_rays_device": (I, [P, P, U32, U64, U32, U32, U32, U32, P, P, P]),
+        "mrt_path_stream": (I, [U64, U32, U32, U32, C.POINTER(C.c_uint64), fp]),
+        "mrt_camera_rays": (I, [C.POINTER(MrtCamera), U32, U32, C.POINTER(C.c_uint32), U32, U64, U32,
+                                C.POINTER(MrtPathRay)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -789,6 +808,36 @@ class Context:
         self._check(lib().mrt_render_views_device(self.h, C.byref(args), arr, n, C.c_void_p(d_rgb),
                                                   C.c_void_p(d_bounces), C.c_void_p(stream or 0)))
 
+    def render_rays(self, rays, seed=1, spp_begin=0, spp_count=1, max_depth=MAX_DEPTH, flags=0, rgb=None,
+                    bounces=None):
+        """mrt_render_rays: whole paths for the caller's rays (a PATH_RAY_DTYPE
+        array, or MrtPathRay objects). Entry i, sample s is Camera::trace of
+        that ray on the stream of (seed, key_i, s) after skip_i draws. Returns
+        (rgb float32 [n*3], bounces uint32 [n]), indexed by list position;
+        accumulates into `rgb` and `bounces` when they are given. The
+        context's camera is neither needed nor changed."""
+        r = path_rays(rays)
+        n = r.shape[0]
+        if rgb is None:
+            rgb = np.zeros(n * 3, dtype=np.float32)
+        if bounces is None:
+            bounces = np.zeros(n, dtype=np.uint32)
+        for a, dt in ((rgb, np.float32), (bounces, np.uint32)):
+            if a.dtype != dt or not a.flags.c_contiguous:
+                raise ValueError("render_rays accumulates in place: contiguous float32 rgb and uint32 bounces")
+        self._check(lib().mrt_render_rays(self.h, r.ctypes.data_as(C.POINTER(MrtPathRay)) if n else None, n, seed,
+                                          spp_begin, spp_count, max_depth, flags, _fptr(rgb),
+                                          bounces.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return rgb, bounces
+
+    def render_rays_device(self, d_rays: int, n_rays: int, seed, spp_begin, spp_count, max_depth, flags, d_rgb: int,
+                           d_bounces: int, stream: int | None = None):
+        """mrt_render_rays_device: the table (n_rays x 32 B, 16-byte aligned) and
+        the accumulation buffers on the device, ordered on `stream`; does not wait."""
+        self._check(lib().mrt_render_rays_device(self.h, C.c_void_p(d_rays), n_rays, seed, spp_begin, spp_count,
+                                                 max_depth, flags, C.c_void_p(d_rgb), C.c_void_p(d_bounces),
+                                                 C.c_void_p(stream or 0)))
+
     def trace_rays(self, rays: np.ndarray, t_min=0.001, t_max=float("inf")):
         r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
         n = r.shape[0]
@@ -907,6 +956,43 @@ def shard_pixels(width: int, height: int, shard_index: int, shard_count: int) ->
     if rc != 0:
         raise MassrtError(lib().mrt_global_last_error().decode())
     return out[: n.value]
+
+
+def path_rays(rays) -> np.ndarray:
+    """A contiguous PATH_RAY_DTYPE array of `rays` (such an array, or a sequence of MrtPathRay)."""
+    if isinstance(rays, np.ndarray):
+        if rays.dtype != PATH_RAY_DTYPE:
+            raise ValueError("rays: a numpy array of massrt.PATH_RAY_DTYPE records")
+        return np.ascontiguousarray(rays).reshape(-1)
+    out = np.zeros(len(rays), dtype=PATH_RAY_DTYPE)
+    for i, r in enumerate(rays):
+        out[i] = (tuple(r.origin), tuple(r.direction), r.key, r.skip)
+    return out
+
+
+def path_stream(seed: int, key: int, sample: int, n: int):
+    """mrt_path_stream: n raw outputs of the stream of (seed, key, sample) and
+    their f32 mapping, (uint64 [n], float32 [n]). Host only."""
+    u = np.zeros(n, dtype=np.uint64)
+    f = np.zeros(n, dtype=np.float32)
+    rc = lib().mrt_path_stream(seed, key, sample, n, u.ctypes.data_as(C.POINTER(C.c_uint64)), _fptr(f))
+    if rc != 0:
+        raise MassrtError(lib().mrt_global_last_error().decode())
+    return u, f
+
+
+def camera_rays(cam: MrtCamera, width: int, height: int, pixels, seed: int = 1, sample: int = 0) -> np.ndarray:
+    """mrt_camera_rays: the renderer's own camera rays of `pixels` (p = y*W + x)
+    for `sample`, as PATH_RAY_DTYPE entries with key = p and skip = the draws
+    each ray took: render_rays over them with spp_begin=sample, spp_count=1 adds
+    what render adds for those pixels and that sample, bit for bit. Host only."""
+    px = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1)
+    out = np.zeros(px.size, dtype=PATH_RAY_DTYPE)
+    rc = lib().mrt_camera_rays(C.byref(cam), width, height, px.ctypes.data_as(C.POINTER(C.c_uint32)), px.size, seed,
+                               sample, out.ctypes.data_as(C.POINTER(MrtPathRay)))
+    if rc != 0:
+        raise MassrtError(lib().mrt_global_last_error().decode())
+    return out
 
 
 DISPLAY_DEFAULT, DISPLAY_DEPTH, DISPLAY_ALBEDO, DISPLAY_NORMAL = 0, 1, 2, 3
