@@ -443,7 +443,9 @@ int mrt_render_views_device(mrt_ctx* ctx, const mrt_render_args* args, const mrt
  *    MRT_ERR_STATE; buffers that do not fit the device are MRT_ERR_NOMEM as
  *    for mrt_render. The _device form cannot inspect its table: its kernel
  *    draws min(skip, MRT_RAY_SKIP_MAX). Ray values are not validated: any
- *    bits are allowed, as for mrt_trace_rays. spp_count == 0 or max_depth == 0
+ *    bits are allowed, as for mrt_trace_rays, and under either traversal
+ *    every hit is the one the reference's walk returns for those bits (a
+ *    NaN or far-away origin included: see mrt_trace_rays). spp_count == 0 or max_depth == 0
  *    adds nothing and returns MRT_OK. MRT_RENDER_COUNTERS and
  *    MRT_RENDER_TIME_KERNELS work as for a frame.
  *  - The call neither needs nor changes the context's camera. On a
@@ -463,7 +465,13 @@ int mrt_camera_rays(const mrt_camera* camera, uint32_t width, uint32_t height, c
                     uint64_t seed, uint32_t sample, mrt_path_ray* out);
 /* rays: n x {ox,oy,oz,dx,dy,dz} host floats; out: n hits. Draws during the
  * traversal (Volume, Mix alpha tests) use ray i's stream keyed
- * (seed 0, i, sample 0xFFFFFFFE). */
+ * (seed 0, i, sample 0xFFFFFFFE). Ray values are not validated, and any bit
+ * pattern returns the reference walk's answer under either traversal: a ray
+ * outside the domain the near-first walk is proven on (a NaN or infinite
+ * origin component, |o| above 2^28, |d| outside [2^-50, 2^28])
+ * takes the reference's walk. Where the reference's own arithmetic overflows
+ * it can accept a hit whose t is NaN; that hit is returned as it is, with
+ * the NaN bits the oracle's host computes. */
 int mrt_trace_rays(mrt_ctx* ctx, const float* rays, uint32_t n, float t_min, float t_max, mrt_hit* out);
 /* The shading probe, mrt_trace_rays one step later: rays as there, out: n
  * records. Ray i draws from one stream keyed (seed, i, sample 0xFFFFFFFD):

@@ -110,6 +110,59 @@ MRT_HD TRay make_tray(V3 o, V3 d, uint32_t scene_flags) {
   return r;
 }
 
+// A NaN t's bits as the oracle's host computes them. The reference's range
+// checks are false on NaN, so a t that is NaN is a hit and its bits are
+// output (far origins: half_b^2 - a*c = inf - inf; a NaN in the ray). The
+// device's instructions need not give the host's NaN: where an operation
+// makes one out of numbers (inf - inf, 0 * inf) v_add / v_mul give 0x7FC00000
+// and the host (x86 SSE) 0xFFC00000, and a NaN operand is not always passed
+// on with the host's sign (seen on the MI355X after the square root and the
+// division, and in the triangle test). Which NaN the walk carries changes no
+// comparison, so the walk is left alone (k_trace sits at its register cap)
+// and mrt_trace_rays' output kernel (trace.hip k_rays_out) computes the
+// winner's expression again where its t is NaN, operation for operation, with
+// every NaN result chosen by the host's rule: the first operand if it is NaN,
+// else the second, else the default NaN 0xFFC00000. Operands in the order of
+// the oracle's source; that this gives the oracle's bits is checked on every
+// NaN t of the adversarial families (tests/test_gpu_adversarial.py).
+// Sphere: the first root if it is NaN (every check on it is false: accepted
+// at once), else the second (the first was a number, and was refused).
+MRT_HD float host_nan(float res, float x, float y) {
+  return x != x ? x : y != y ? y : res != res ? u2f(0xFFC00000u) : res;
+}
+MRT_HD float hn_sub(float x, float y) { return host_nan(x - y, x, y); }
+MRT_HD float hn_add(float x, float y) { return host_nan(x + y, x, y); }
+MRT_HD float hn_mul(float x, float y) { return host_nan(x * y, x, y); }
+MRT_HD float hn_div(float x, float y) { return host_nan(x / y, x, y); }
+MRT_HD float hn_dot(V3 x, V3 y) { return hn_add(hn_add(hn_mul(x.x, y.x), hn_mul(x.y, y.y)), hn_mul(x.z, y.z)); }
+MRT_HD V3 hn_cross(V3 x, V3 y) {
+  return V3{hn_sub(hn_mul(x.y, y.z), hn_mul(x.z, y.y)), hn_sub(hn_mul(x.z, y.x), hn_mul(x.x, y.z)),
+            hn_sub(hn_mul(x.x, y.y), hn_mul(x.y, y.x))};
+}
+MRT_HD float sphere_root_nan(V3 c, float r, V3 o, V3 d) {
+  const float a = hn_dot(d, d);
+  const V3 oc{hn_sub(o.x, c.x), hn_sub(o.y, c.y), hn_sub(o.z, c.z)};
+  const float half_b = hn_dot(oc, d);
+  const float cc = hn_sub(hn_dot(oc, oc), hn_mul(r, r));
+  const float disc = hn_sub(hn_mul(half_b, half_b), hn_mul(a, cc));
+  const float sq = disc != disc ? disc : sqrtf(disc);
+  const float first = hn_div(hn_sub(-half_b, sq), a);
+  return first != first ? first : hn_div(hn_add(-half_b, sq), a);
+}
+// the same for a triangle's t (Triangle::intersect's expression, tri_hit) and
+// for the ray an instance's inverse makes (xform)
+MRT_HD float tri_t_nan(V3 a, V3 ab, V3 ac, V3 o, V3 d) {
+  const float inv_det = hn_div(1.0f, hn_dot(ab, hn_cross(d, ac)));
+  const V3 t_vec{hn_sub(o.x, a.x), hn_sub(o.y, a.y), hn_sub(o.z, a.z)};
+  return hn_mul(hn_dot(ac, hn_cross(t_vec, ab)), inv_det);
+}
+MRT_HD V3 xform_nan(V3 c0, V3 c1, V3 c2, V3 c3, V3 p, float w) {
+  auto row = [&](float k0, float k1, float k2, float k3) {
+    return hn_add(hn_add(hn_add(hn_mul(k0, p.x), hn_mul(k1, p.y)), hn_mul(k2, p.z)), hn_mul(k3, w));
+  };
+  return V3{row(c0.x, c1.x, c2.x, c3.x), row(c0.y, c1.y, c2.y, c3.y), row(c0.z, c1.z, c2.z, c3.z)};
+}
+
 MRT_HD bool sphere_hit(V3 c, float r, V3 o, V3 d, const Recip& ra, float tmin, float tmax, float& t) {
   V3 oc = o - c;
   float a = ra.b;  // length_squared(d), precomputed per ray

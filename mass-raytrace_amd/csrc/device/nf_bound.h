@@ -59,6 +59,19 @@ struct NfBound {
 // ray takes the reference's walk from the start (always exact).
 constexpr float kNfKappaMax = 0x1p-8f;
 constexpr float kNfAMax = 0x1p-4f;
+// The bound is derived without overflow (DESIGN.md §4 "The proof's domain"):
+// a ray walks near first only if its origin is finite with |o| at most
+// kNfOriginMax and 2^-50 <= |d| <= kNfDirMax (so |o| |d| <= 2^56), and the
+// trees are built only for a scene whose world boxes lie within kNfCoordMax
+// per coordinate and whose instances keep an object ray within the same kind
+// of limits (nf_tree.cpp) — then no intermediate of the sphere test, the
+// triangle test or the instance transform overflows, in either space.
+constexpr float kNfOriginMax = 0x1p28f;
+constexpr float kNfDirMax = 0x1p28f;
+constexpr float kNfCoordMax = 0x1p28f;    // every world box coordinate (the slab test's early domain too, isect.h)
+constexpr float kNfInvNormMax = 0x1p16f;   // an instance's |inv| (Frobenius, 3x3 part; Cornell's thin light: 1e4)
+constexpr float kNfInvShiftMax = 0x1p44f;  // an instance's |inv translation|
+constexpr float kNfObjRadMax = 0x1p12f;    // an instanced BLAS lies within this of its origin
 
 
 // A ray's rho as a function of t (the walk's bound on the t of the hits it
@@ -95,11 +108,14 @@ MRT_HD float nf_min(float a, float b) {
 #endif
 }
 
-// may this ray (world space, |d|^2 = d2) take the near-first walk?
-MRT_HD bool nf_ray_ok(const NfBound& B, float d2) {
+// may this ray (world space, origin o, |d|^2 = d2) take the near-first walk?
+// Once per ray (walk.h nf_start). A NaN or an infinity anywhere in o makes
+// |o| NaN or +inf, as does a component whose square overflows: every
+// comparison is written so that it fails on NaN.
+MRT_HD bool nf_ray_ok(const NfBound& B, V3 o, float d2) {
   const float dl = nf_sqrt_up(d2);
   return d2 >= 0x1p-100f && B.kw1 * dl <= B.kmax && B.ko1 * dl <= B.kmax && B.aw0 + B.aw1 * dl <= kNfAMax &&
-         dl < INFINITY;
+         dl <= kNfDirMax && nf_len(o) <= kNfOriginMax;
 }
 
 // The world-space coefficients of a ray (o, |d|^2 = d2): a generic or

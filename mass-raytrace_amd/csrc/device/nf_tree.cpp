@@ -523,6 +523,17 @@ struct Builder {
     m.ko = ob.k1 * ng * (1 + g3);
     return m;
   }
+  // Does the instance keep an object-space ray inside the bound's domain
+  // (nf_bound.h kNfInvNormMax, kNfInvShiftMax; NaN: no)? With |o| <= 2^28 and
+  // |d| <= 2^28 in world space: |o'| <= 2^16 2^28 + 2^44 and |d'| <= 2^44.
+  bool inst_in_domain(uint32_t id) const {
+    const float* G = d.instances[id].inv;
+    double ng = 0, gt = 0;
+    for (int c = 0; c < 3; ++c)
+      for (int r = 0; r < 3; ++r) ng += (double)G[4 * c + r] * G[4 * c + r];
+    for (int r = 0; r < 3; ++r) gt += (double)G[12 + r] * G[12 + r];
+    return std::sqrt(ng) <= kNfInvNormMax && std::sqrt(gt) <= kNfInvShiftMax;
+  }
   // a wild instance: its terms would dominate the world margin; the walk
   // never culls it (and its subtree) instead
   static bool wild(const InstTerm& m) { return m.w0 > 0x1p-14 || m.w1 > 0x1p-14 || m.b1 > 0x1p-14; }
@@ -720,6 +731,14 @@ struct Builder {
       TriBound tb;
       const Box b = object_box(r, kd == KIND_TRI ? &tb : nullptr);
       keep_box(r, b);
+      // the domain the rounding bound is derived on (nf_bound.h kNfCoordMax,
+      // DESIGN.md §4): a world the walk's arithmetic could overflow on keeps
+      // the reference's walk
+      for (int k = 0; k < 3; ++k)
+        if (!(std::fabs(b.mn[k]) <= kNfCoordMax && std::fabs(b.mx[k]) <= kNfCoordMax))
+          return (s.nf_note = "a world box outside the rounding bound's domain (2^28)", true);
+      if (kd == KIND_INST && !inst_in_domain(rec::object_id(ws(), r)))
+        return (s.nf_note = "an instance transform outside the rounding bound's domain", true);
       if (kd == KIND_TRI) grow_bound(world_tri, tb);
       bool generic = tb.a1 > 0;
       if (kd == KIND_INST || kd == KIND_MODEL) {
@@ -762,6 +781,7 @@ struct Builder {
     }
     aw0 = std::max(aw0, world_tri.a0), aw1 = std::max(aw1, world_tri.a1);
     if (r_min < 0x1p-60) return (s.nf_note = "a sphere too small for the walk's rounding bound", true);
+    if (!(orad <= kNfObjRadMax)) return (s.nf_note = "an instanced mesh outside the rounding bound's domain (2^12)", true);
     // The world tree holds the other items only: no forced path, and its
     // boxes do not span the wild items' boxes. The wild items get a tree of
     // their own, every child of it forced, which a ray walks last — its root

@@ -249,6 +249,27 @@ __global__ __launch_bounds__(kBlock) void k_rays_out(DevScene S, PathBufs in, co
   LocalCounters lc;  // a mapped normal decides front_face (EXT): its taps are not counted
   if (h.prim != kRefNone)
     front = resolve_hit<EXT>(S, V3{o4.x, o4.y, o4.z}, V3{d4.x, d4.y, d4.z}, h, lc).front_face ? 1u : 0u;
+  // a NaN t (the reference's range checks are false on it: a hit): the bits
+  // the oracle's host computes, which the device's own instructions need not
+  // give (isect.h host_nan) — the winner's expression again by the host's rules
+  if (h.prim != kRefNone && h.t != h.t) {
+    V3 o{o4.x, o4.y, o4.z}, d{d4.x, d4.y, d4.z};
+    const uint32_t pkind = h.prim >> 28, pidx = h.prim & 0x0FFFFFFFu;
+    if (pkind == MRT_REF_SPHERE) {  // spheres are world objects
+      const uint32_t sp = MRT_IDX(S, pidx, S.n_sph, 10);
+      h.t = sphere_root_nan(ld3(S.sph + (size_t)sp * 4), S.sph[(size_t)sp * 4 + 3], o, d);
+    } else if (pkind == MRT_REF_TRIANGLE) {
+      if ((h.container >> 28) == MRT_REF_INSTANCE) {
+        V3 c0, c1, c2, c3;
+        load_m12(S.inst_inv + (size_t)MRT_IDX(S, h.container & 0x0FFFFFFFu, S.n_inst, 9) * 12, c0, c1, c2, c3);
+        const V3 wo = o, wd = d;
+        o = xform_nan(c0, c1, c2, c3, wo, 1.0f);
+        d = xform_nan(c0, c1, c2, c3, wd, 0.0f);
+      }
+      const TriShade tr = load_tri(S, pidx);
+      h.t = tri_t_nan(tr.a, tr.b - tr.a, tr.c - tr.a, o, d);
+    }
+  }
   out[i] = make_uint4(h.prim, h.container, __float_as_uint(h.prim != kRefNone ? h.t : 0.0f), front);
 }
 

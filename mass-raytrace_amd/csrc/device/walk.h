@@ -225,7 +225,9 @@ MRT_HD void nf_push(const NfStack& k, Trav& t, uint32_t v) {
 #define MRT_PIN_VGPR(x) (void)0
 #endif
 // the walk starts at the NF world tree (trav_init_nf): rays its bound does not
-// cover take the reference's walk instead, and push nothing. WILD (the scene
+// cover (nf_bound.h nf_ray_ok: the generic kappa, and the domain the bound is
+// proven on — a finite origin within 2^28, |d| in [2^-50, 2^28]) take the
+// reference's walk instead, and push nothing. WILD (the scene
 // has a wild tree, layout.h nf_wild_root; k_trace's variant for such scenes):
 // the ray first pushes kNfWildMark. LIFO order pops it when everything else
 // is done, so a wild leaf, which nothing above it culls, has its own box test
@@ -235,7 +237,7 @@ MRT_HD void nf_push(const NfStack& k, Trav& t, uint32_t v) {
 // tested. Scenes without a wild tree compile none of this.
 template <bool WILD>
 MRT_HD void nf_start(const TravIn& in, const NfStack& k, Trav& t) {
-  if (nf_ray_ok(in.S.nfb, t.r.a.b)) {
+  if (nf_ray_ok(in.S.nfb, t.r.o, t.r.a.b)) {
     if (WILD) {
       uint32_t mark = kNfWildMark;
       MRT_PIN_VGPR(mark);

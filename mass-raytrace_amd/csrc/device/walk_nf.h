@@ -10,7 +10,9 @@
 // reference's own f32 arithmetic, on how far a primitive's computed hit can
 // lie outside its box — so the walk meets every primitive whose computed t is
 // at most cull(best). Rays the bound does not cover (a
-// generic triangle's kappa above kNfKappaMax) take the reference's walk.
+// generic triangle's kappa above kNfKappaMax; an origin that is not finite
+// or lies beyond 2^28, |d| outside [2^-50, 2^28]: nf_bound.h nf_ray_ok) take
+// the reference's walk.
 #pragma once
 #include "walk.h"
 

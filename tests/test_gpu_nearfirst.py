@@ -13,7 +13,8 @@ import pytest
 
 import massrt
 import oracle
-from test_gpu_parity import ASPECT, MESH, RTOL, SMALL, _alpha_plane, build_both, camera_rays, random_rays, rel_l2
+from adversarial_rays import alpha_world, build_both, wild_world  # the worlds the adversarial-ray tests walk too
+from test_gpu_parity import ASPECT, MESH, RTOL, SMALL, camera_rays, random_rays, rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -75,20 +76,7 @@ def test_render_equals_the_reference_walk(nf_ctx, small, golden_dir, scene):
 def test_alpha_mesh_through_model_and_instance(nf_ctx, variant):
     """Alpha-tested triangles in a BLAS entered through a Model and/or an
     Instance (the order keys of BLAS primitives, the object-space check)."""
-    tex, tris = _alpha_plane(np.random.default_rng(7))
-
-    def scene(x):
-        st = x.texture_rgba(tex, massrt.WRAP_REPEAT)
-        x.background(massrt.BG_SKY)
-        mt = x.material(massrt.MAT_LAMBERTIAN, st)
-        m = x.model(mt, tris, add_to_world=variant in ("model", "both"), shading=True)
-        if variant in ("instance", "both"):
-            x.add_instance(m, (0.5, 0.2, -1.5), (0.1, 0.2, 0.05), (1.2, 0.8, 1.0), x.material(massrt.MAT_METAL, st, 0.3))
-        x.add_sphere(x.material(massrt.MAT_DIELECTRIC, 0, 1.4), (0.3, 0.1, 1.0), 0.5)
-        x.build_bvh()
-        x.camera(45.0, (0.5, 0.8, 6), (0, 0, 0), aspect=ASPECT)
-
-    b, o = build_both(scene)
+    b, o = build_both(lambda x: alpha_world(x, variant, ASPECT))
     nf_ctx.upload(b)
     assert nf_ctx.tuning()["traversal"] == massrt.TRAVERSAL_NEAR_FIRST
     r = np.random.default_rng(3)
@@ -105,23 +93,7 @@ def test_wild_instances(nf_ctx, golden_dir):
     bound into the instance's BLAS (path.h nf_node_test). Thin
     slabs scaled 1:3000, crossing each other, non-wild cubes and spheres, rays
     from everywhere — and grazing the slabs — against the oracle."""
-    def scene(x):
-        x.background(massrt.BG_SKY)
-        lam = x.material(massrt.MAT_LAMBERTIAN, x.solid(0.6, 0.5, 0.4))
-        glow = x.material(massrt.MAT_DIFFUSE_LIGHT, 0, 0.0, (4.0, 4.0, 4.0))
-        cube = x.model_from_ply(golden_dir / "cube.ply", lam)
-        for k in range(6):  # wild: 12 x 0.004 x 9
-            x.add_instance(cube, (0.7 * k - 2.0, 0.3 * k - 0.6, -0.5 * k), (0.1 * k, 0.05, 0.02 * k), (12.0, 0.004, 9.0),
-                           glow if k % 2 else NO_MAT)
-        for k in range(5):  # ordinary
-            x.add_instance(cube, (1.1 * k - 2.0, 0.2, 1.0 - 0.4 * k), (0.0, 0.13 * k, 0.0), (0.4, 0.4, 0.4))
-        for k in range(4):
-            x.add_sphere(x.material(massrt.MAT_METAL, x.solid(0.8, 0.8, 0.8), 0.1), (k - 1.5, -0.2, 0.3 * k), 0.35)
-        x.build_bvh()
-        x.camera(45.0, (0.5, 1.5, 7), (0, 0, 0), aspect=ASPECT)
-
-    NO_MAT = massrt.NO_MATERIAL
-    b, o = build_both(scene)
+    b, o = build_both(lambda x: wild_world(x, golden_dir, ASPECT))
     nf_ctx.upload(b)
     assert nf_ctx.tuning()["traversal"] == massrt.TRAVERSAL_NEAR_FIRST
     r = np.random.default_rng(5)

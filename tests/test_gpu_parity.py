@@ -11,6 +11,7 @@ import pytest
 
 import massrt
 import oracle
+from adversarial_rays import alpha_plane as _alpha_plane, build_both  # shared with the adversarial-ray tests
 from conftest import walk_keys
 from ray_gen import camera_rays, random_rays
 
@@ -132,13 +133,6 @@ def test_depth_limits(ctx, small_scenes):
         assert g[1].max() <= 2 * depth
 
 
-def build_both(fn):
-    b, o = massrt.Builder(3), oracle.Scene(3)
-    fn(b)
-    fn(o)
-    return b, o
-
-
 @pytest.mark.parametrize("kind,param", [(massrt.MAT_LAMBERTIAN, 0.0), (massrt.MAT_METAL, 0.0),
                                         (massrt.MAT_DIELECTRIC, 1.5)])
 def test_furnace_exact_on_gpu(ctx, kind, param):
@@ -209,22 +203,6 @@ def test_backgrounds_textures_and_alpha(ctx):
         if "model_entries" in walk_keys(ctx, ["model_entries"]):
             assert gc["model_entries"] == oc["model_entries"]
         assert oc["alpha_taps"] > 0
-
-
-def _alpha_plane(rng):
-    tex = rng.integers(0, 256, size=(16, 24, 4), dtype=np.uint8)
-    tex[..., 3] = np.where(rng.random((16, 24)) < 0.3, 0, 255)
-    grid = np.linspace(-2, 2, 9, dtype=np.float32)
-    tris = []
-    for i in range(8):
-        for j in range(8):
-            x0, x1, y0, y1 = grid[i], grid[i + 1], grid[j], grid[j + 1]
-            for tri in ([[x0, y0, 0], [x1, y0, 0], [x1, y1, 0]], [[x0, y0, 0], [x1, y1, 0], [x0, y1, 0]]):
-                row = []
-                for v in tri:
-                    row += list(v) + [0, 0, 1] + [v[0] * 0.3 + 0.5, v[1] * 0.3 + 0.5]
-                tris.append(row)
-    return tex, np.array(tris, dtype=np.float32)
 
 
 @pytest.mark.parametrize("variant", ["model", "instance", "both"])

@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import adversarial_rays
 import massrt
 import oracle
 from conftest import GOLDEN, REPO
@@ -232,3 +233,38 @@ def test_host_walks_equal_the_oracle(slab_check, scene, tmp_path):
     for walk in WALKS:
         hits = _host_hits(slab_check, scene, walk, rays, tmp_path)
         assert np.array_equal(hits, want), f"{walk}: {int((hits != want).any(1).sum())} rays differ"
+
+
+# ---- adversarial rays (tests/adversarial_rays.py): zero and tiny direction components, origins on box
+# planes, box corners, triangle edges, sphere centres and tangents, |d| from 2^-120 to 2^100, origins up
+# to 1e38 away, NaN and infinities. The reference's own arithmetic overflows on some of them and accepts
+# hits whose t is NaN; both walks must return exactly what the oracle does.
+@pytest.fixture(scope="module")
+def adversarial():
+    """scene -> (rays of all families, (family, begin, end) offsets, the oracle's hits), computed once per scene;
+    the oracle's answers hold enough hits per family to prove something (adversarial_rays.check_floors)."""
+    cache = {}
+
+    def get(scene):
+        if scene not in cache:
+            aspect = float(massrt.ASPECT_RATIO)
+            b = massrt.Builder(1).builtin(scene, aspect, GOLDEN)  # desc() points into the builder: kept until used
+            rays, parts = adversarial_rays.split(adversarial_rays.families(*b.desc()))
+            want = oracle.Scene(1).builtin(scene, aspect, GOLDEN).trace_rays(rays)
+            cache[scene] = rays, parts, want
+        return cache[scene]
+    return get
+
+
+@pytest.mark.parametrize("walk", WALKS)
+@pytest.mark.parametrize("scene", SMALL)
+def test_host_walks_adversarial_rays(slab_check, adversarial, scene, walk, tmp_path):
+    """Every family through one run of the host walk: all four words of every ray equal the oracle's."""
+    rays, parts, want = adversarial(scene)
+    assert {name for name, _, _ in parts} == {f.__name__ for f in adversarial_rays.FAMILIES}
+    adversarial_rays.check_floors({name: want[a:e] for name, a, e in parts}, overflow=scene != "cube_field")
+    hits = _host_hits(slab_check, scene, walk, rays, tmp_path)
+    assert hits.shape == want.shape
+    bad = [m for m in (adversarial_rays.first_difference(name, rays[a:e], hits[a:e], want[a:e]) for name, a, e in parts)
+           if m]
+    assert not bad, f"{walk} on {scene}:\n" + "\n".join(bad)
