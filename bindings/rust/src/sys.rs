@@ -390,6 +390,26 @@ pub struct mrt_denoise_params {
     pub sigma_normal: f32,
 }
 
+/// The rule of `mrt_render_adaptive` (mrt_adaptive_default_params: 16, 128, 0.05, 0.01).
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct mrt_adaptive_params {
+    pub min_spp: u32,
+    pub step_spp: u32,
+    pub threshold: f32,
+    pub floor: f32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default, Debug)]
+pub struct mrt_adaptive_report {
+    pub rounds: u32,
+    pub spp_reached: u32,
+    pub tiles: u32,
+    pub tiles_open: u32,
+    pub samples: u64,
+}
+
 /// Opaque handles.
 #[repr(C)]
 pub struct mrt_ctx {
@@ -436,6 +456,25 @@ extern "C" {
     pub fn mrt_path_stream(seed: u64, key: u32, sample: u32, n: u32, out_u64: *mut u64, out_f32: *mut f32) -> i32;
     pub fn mrt_camera_rays(camera: *const mrt_camera, width: u32, height: u32, pixels: *const u32, n: u32, seed: u64,
                            sample: u32, out: *mut mrt_path_ray) -> i32;
+    pub fn mrt_adaptive_default_params(out: *mut mrt_adaptive_params) -> i32;
+    pub fn mrt_render_adaptive(ctx: *mut mrt_ctx, args: *const mrt_render_args, params: *const mrt_adaptive_params,
+                               accum_rgb: *mut f32, accum_bounces: *mut u32, moments: *mut f32, samples: *mut u32,
+                               report: *mut mrt_adaptive_report) -> i32;
+    pub fn mrt_render_adaptive_device(ctx: *mut mrt_ctx, args: *const mrt_render_args,
+                                      params: *const mrt_adaptive_params, d_accum_rgb: *mut f32,
+                                      d_accum_bounces: *mut u32, d_moments: *mut f32, d_samples: *mut u32,
+                                      report: *mut mrt_adaptive_report, hip_stream: *mut c_void) -> i32;
+    pub fn mrt_adaptive_tiles(width: u32, height: u32, shard_index: u32, shard_count: u32, moments: *const f32,
+                              samples: *const u32, params: *const mrt_adaptive_params, open: *mut u8,
+                              n_open: *mut u32) -> i32;
+    pub fn mrt_adaptive_tiles_device(ctx: *mut mrt_ctx, width: u32, height: u32, shard_index: u32, shard_count: u32,
+                                     d_moments: *const f32, d_samples: *const u32,
+                                     params: *const mrt_adaptive_params, d_open: *mut u8, d_n_open: *mut u32,
+                                     hip_stream: *mut c_void) -> i32;
+    pub fn mrt_adaptive_resolve(ctx: *mut mrt_ctx, width: u32, height: u32, accum_rgb: *const f32,
+                                samples: *const u32, out_rgb: *mut f32) -> i32;
+    pub fn mrt_adaptive_resolve_device(ctx: *mut mrt_ctx, width: u32, height: u32, d_accum_rgb: *const f32,
+                                       d_samples: *const u32, d_out_rgb: *mut f32, hip_stream: *mut c_void) -> i32;
     pub fn mrt_trace_rays(ctx: *mut mrt_ctx, rays: *const f32, n: u32, t_min: f32, t_max: f32, out: *mut mrt_hit)
         -> i32;
     pub fn mrt_get_counters(ctx: *mut mrt_ctx, out: *mut mrt_counters) -> i32;

@@ -463,6 +463,102 @@ int mrt_render_rays_device(mrt_ctx* ctx, const mrt_path_ray* d_rays, uint32_t n_
 int mrt_path_stream(uint64_t seed, uint32_t key, uint32_t sample, uint32_t n, uint64_t* out_u64, float* out_f32);
 int mrt_camera_rays(const mrt_camera* camera, uint32_t width, uint32_t height, const uint32_t* pixels, uint32_t n,
                     uint64_t seed, uint32_t sample, mrt_path_ray* out);
+/* ---- adaptive sampling ----------------------------------------------------
+ * mrt_render with a noise target and a sample cap: every MRT_TILE x MRT_TILE
+ * tile of the shard is sampled in rounds until its estimated error is met or
+ * args->spp_count samples per pixel (the cap) are spent. A pixel that stops
+ * after n samples holds exactly what mrt_render adds for spp_count = n: the
+ * same streams (seed, pixel, sample), the same sums in sample order, bit for
+ * bit. A stopping rule that looks at the samples it stops on biases the
+ * estimate (tiles that happen to look calm stop early): the standard trade of
+ * adaptive sampling, smaller for a larger min_spp.
+ * All arithmetic below is IEEE f32, uncontracted, in the order written:
+ * + - * and comparisons only.
+ *  - Per sample, (r, g, b) the colour mrt_render adds: y = (r + g) + b, and
+ *    per pixel in sample order m1 += y, m2 += y * y, n += 1.
+ *  - Buffers: moments = width*height*2 floats, {m1, m2} of pixel
+ *    p = y*width + x (y = 0 the bottom row, as the accumulation buffers);
+ *    samples = width*height counts n. Both are the caller's and, like
+ *    accum_rgb, are ADDED to; decisions read them as they stand. Zeroed
+ *    buffers start a fresh estimate, the same buffers again continue one.
+ *  - Decision for a tile; slot i = (y % 8)*8 + (x % 8), a slot without a pixel
+ *    (edge tiles) contributes +0.0 to both sums. Per pixel, nf = (float)n,
+ *    tau2 = threshold * threshold:
+ *      L = nf * m2 - m1 * m1
+ *      q = m1 + nf * floor
+ *      R = (tau2 * (nf - 1.0f)) * (q * q)
+ *    The 64 L and the 64 R are each summed by the tree: for k = 32, 16, 8, 4,
+ *    2, 1: v[i] = v[i] + v[i + k], i < k. The tile is CLOSED iff every present
+ *    pixel has n >= 2 and L_sum <= R_sum; any NaN leaves it open. In words:
+ *    the tile's RMS standard error of the mean is at most `threshold` times
+ *    its RMS of (mean + floor), means in units of y.
+ *  - Rounds over the tiles of the shard (shard_index, shard_count; in
+ *    mrt_shard_pixels' order). Round 0 adds samples [spp_begin, spp_begin +
+ *    min_spp) to every tile (min_spp == 0: nothing). After each round every
+ *    tile still in the running is evaluated; a closed tile leaves for the rest
+ *    of the call. Round r >= 1 adds the next min(step_spp, cap - done) sample
+ *    indices to the pixels of the open tiles, done = the samples per pixel
+ *    given so far in this call. The call ends when no tile is open or
+ *    done == cap; the last round is evaluated too, for the report. Sample
+ *    indices depend on the round alone.
+ *  - So: shards into shared buffers equal one call, the size of the results
+ *    slab changes nothing, and a call capped at 16 followed by one with
+ *    min_spp = 0, spp_begin + 16 and cap 16 equals one call capped at 32.
+ *  - mrt_render_adaptive_device takes device pointers and is ordered on
+ *    `hip_stream`. It reads one word per round (the open tiles' pixel count),
+ *    so unlike mrt_render_device it RETURNS WHEN THE RENDER HAS ENDED (the
+ *    work is complete on the device). report may be NULL: rounds run, the
+ *    largest done (spp_reached), the shard's tiles, those still open after
+ *    the last evaluation, and the samples added over all pixels.
+ *  - mrt_adaptive_tiles is the decision alone, host only, no context: one byte
+ *    per tile of the shard in shard order, 1 = open; n_open (may be NULL) the
+ *    number open; only threshold and floor of params are read.
+ *    mrt_adaptive_tiles_device: the same from device buffers into a device
+ *    byte array, ordered on `hip_stream`; d_n_open (device word, may be NULL).
+ *  - mrt_adaptive_resolve: out[3p+c] = (1.0f / (float)samples[p]) *
+ *    accum_rgb[3p+c], zeros where samples[p] == 0: the Default tonemap's own
+ *    scale * sum, so mrt_tonemap*(out, passes = 1, MRT_DISPLAY_DEFAULT) gives
+ *    pixel p the byte of the uniform samples[p]-spp frame, and mrt_denoise*
+ *    takes out with passes = 1. The sample map displays as it stands through
+ *    mrt_tonemap*(.., accum_bounces = samples, passes = 1, MRT_DISPLAY_DEPTH).
+ *  - MRT_ERR_INVALID before anything is enqueued: a null params or buffer,
+ *    min_spp > spp_count, step_spp == 0, more than 4096 rounds, a threshold or
+ *    floor that is negative, NaN or infinite, MRT_RENDER_FUSED or
+ *    MRT_RENDER_SIMPLE_TRACE, spp_begin + spp_count > 2^32 - 1, a shard of more
+ *    than 2^26 tiles. MRT_ERR_STATE without a scene or camera. spp_count == 0
+ *    or max_depth == 0 adds nothing, zeroes the report and returns MRT_OK.
+ *    MRT_RENDER_COUNTERS and MRT_RENDER_TIME_KERNELS work as for a frame.
+ *  - The call neither needs more than the context's camera nor changes it. On
+ *    a multi-device context it runs on device 0; callers shard.
+ * Defaults: min_spp 16, step_spp 128, threshold 0.05, floor 0.01. Every round
+ * drains the wavefront loop once (tens of milliseconds at 1920x1080, whatever
+ * the step): a small step buys finer stopping at that price per round. */
+typedef struct {
+  uint32_t min_spp, step_spp;
+  float threshold, floor;
+} mrt_adaptive_params;
+typedef struct {
+  uint32_t rounds, spp_reached, tiles, tiles_open;
+  uint64_t samples;
+} mrt_adaptive_report;
+int mrt_adaptive_default_params(mrt_adaptive_params* out);
+int mrt_render_adaptive(mrt_ctx* ctx, const mrt_render_args* args, const mrt_adaptive_params* params,
+                        float* accum_rgb, uint32_t* accum_bounces, float* moments, uint32_t* samples,
+                        mrt_adaptive_report* report);
+int mrt_render_adaptive_device(mrt_ctx* ctx, const mrt_render_args* args, const mrt_adaptive_params* params,
+                               float* d_accum_rgb, uint32_t* d_accum_bounces, float* d_moments, uint32_t* d_samples,
+                               mrt_adaptive_report* report, void* hip_stream);
+int mrt_adaptive_tiles(uint32_t width, uint32_t height, uint32_t shard_index, uint32_t shard_count,
+                       const float* moments, const uint32_t* samples, const mrt_adaptive_params* params,
+                       uint8_t* open, uint32_t* n_open);
+int mrt_adaptive_tiles_device(mrt_ctx* ctx, uint32_t width, uint32_t height, uint32_t shard_index,
+                              uint32_t shard_count, const float* d_moments, const uint32_t* d_samples,
+                              const mrt_adaptive_params* params, uint8_t* d_open, uint32_t* d_n_open,
+                              void* hip_stream);
+int mrt_adaptive_resolve(mrt_ctx* ctx, uint32_t width, uint32_t height, const float* accum_rgb,
+                         const uint32_t* samples, float* out_rgb);
+int mrt_adaptive_resolve_device(mrt_ctx* ctx, uint32_t width, uint32_t height, const float* d_accum_rgb,
+                                const uint32_t* d_samples, float* d_out_rgb, void* hip_stream);
 /* rays: n x {ox,oy,oz,dx,dy,dz} host floats; out: n hits. Draws during the
  * traversal (Volume, Mix alpha tests) use ray i's stream keyed
  * (seed 0, i, sample 0xFFFFFFFE). Ray values are not validated, and any bit

@@ -153,6 +153,8 @@ int mrt_destroy(mrt_ctx* c) {
   if (c->set_fork) hipEventDestroy(c->set_fork);
   if (c->rays_ready) hipEventDestroy(c->rays_ready);
   if (c->ids_ready) hipEventDestroy(c->ids_ready);
+  if (c->ad_ev) hipEventDestroy(c->ad_ev);
+  if (c->ad_words_h) hipHostFree(c->ad_words_h);
   for (Queue& q : c->q) {
     if (q.h_stat) hipHostFree(q.h_stat);
     for (hipEvent_t e : {q.ev[0], q.ev[1], q.join})

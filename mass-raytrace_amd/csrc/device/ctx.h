@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../../include/massrt.h"
+#include "../host/adaptive.h"
 #include "../host/loop.h"
 #include "../host/options.h"
 #include "devmem.h"
@@ -52,6 +53,12 @@ struct Queue {
   HostStatus* d_stat = nullptr;  // the same memory as the device addresses it
   hipEvent_t ev[2]{};
   hipEvent_t join = nullptr;
+};
+
+// A round's word of mrt_render_adaptive: the pixels and the tiles still open
+// after its evaluation, the next round's list length among them.
+struct AdaptWord {
+  uint32_t pixels, tiles;
 };
 
 struct mrt_ctx {
@@ -117,9 +124,21 @@ struct mrt_ctx {
   hipEvent_t ids_ready = nullptr;
   DevBuf<mrt_path_ray> rays_d;
   hipEvent_t rays_ready = nullptr;
+  // mrt_render_adaptive: a byte per shard tile (1: still in the running), the scan's words (an offset per tile, then
+  // {pixels, open tiles} per kBlock tiles), the next round's pixel list (two, alternating), and one word per round
+  // that k_adaptive_scan_blocks writes into pinned host memory and the host reads behind ad_ev. All grown on demand
+  // (adaptive_scratch); a call returns only when its kernels have ended, so between calls nothing reads them
+  DevBuf<uint8_t> ad_open;
+  DevBuf<uint32_t> ad_scan;
+  DevBuf<uint32_t> ad_list[2];
+  AdaptWord* ad_words_h = nullptr;  // pinned coherent, kAdaptMaxRounds words
+  AdaptWord* ad_words_d = nullptr;  // the same memory as the device addresses it
+  hipEvent_t ad_ev = nullptr;
   // host-buffer render staging
   DevBuf<float> d_acc_rgb;
   DevBuf<uint32_t> d_acc_b;
+  DevBuf<float> d_acc_mom;     // mrt_render_adaptive's moments and counts
+  DevBuf<uint32_t> d_acc_n;
   // kernel timing
   std::vector<hipEvent_t> ev_pool;
   size_t ev_used = 0;
@@ -222,3 +241,14 @@ void render_views_device(mrt_ctx* c, const mrt_render_args* a, const mrt_view* v
                          uint32_t* d_b, hipStream_t st);
 mrt::DevCamera dev_camera(const mrt_camera& cam);
 void resolve_kernel_timing(mrt_ctx* c);
+
+// ---- adaptive.hip ----
+// k_accumulate with the moments and counts of mrt_render_adaptive beside the sums (render_wavefront's other accumulate)
+void accumulate_moments(mrt_ctx* c, const RenderParams& rp, float* d_rgb, uint32_t* d_b, float* d_moments,
+                        uint32_t* d_samples, hipStream_t st);
+mrt::AdaptFrame adaptive_frame(mrt_ctx* c, uint32_t W, uint32_t H, uint32_t si, uint32_t sc);  // checked
+void adaptive_scratch(mrt_ctx* c, uint32_t n_tiles, uint32_t n_pix);
+void adaptive_evaluate(const mrt::AdaptFrame& f, const float* d_moments, const uint32_t* d_samples, float tau2,
+                       float floor, uint8_t* d_open, bool only_running, uint32_t* d_n_open, hipStream_t st);
+AdaptWord adaptive_compact(mrt_ctx* c, const mrt::AdaptFrame& f, uint32_t* list, uint32_t list_cap, uint32_t round,
+                           hipStream_t st);

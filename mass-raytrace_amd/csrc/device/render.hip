@@ -532,9 +532,19 @@ void launch_finish(mrt_ctx* c, int qi, uint32_t cur, const RenderParams& rp, boo
   HIP_CHECK(hipGetLastError());
 }
 
+// The accumulate a wavefront render folds its slab with: plain k_accumulate,
+// or (moments set) adaptive.hip's, which adds the moments and counts of
+// mrt_render_adaptive beside the same sums.
+struct Accum {
+  float* moments = nullptr;
+  uint32_t* samples = nullptr;
+};
+
 // Folds a chunk's results slab into the caller's accumulation buffers on `st`
 // (k_accumulate: in sample order).
-void accumulate(mrt_ctx* c, const RenderParams& rp, float* d_rgb, uint32_t* d_b, hipStream_t st) {
+void accumulate(mrt_ctx* c, const RenderParams& rp, float* d_rgb, uint32_t* d_b, hipStream_t st,
+                const Accum& acc = Accum{}) {
+  if (acc.moments) return accumulate_moments(c, rp, d_rgb, d_b, acc.moments, acc.samples, st);
   hipLaunchKernelGGL(k_accumulate, dim3((rp.n_pix + kAccPix - 1) / kAccPix), dim3(kBlock), 0, st,
                      (const float4*)c->results.p, rp.n_pix, rp.spp, rp.pixlist, d_rgb, d_b);
   HIP_CHECK(hipGetLastError());
@@ -857,9 +867,10 @@ namespace {
 // The drain hand-off needs no camera under either table: launch_finish's
 // kernel only adopts live paths (ADOPT: gen_work is not in it), so the
 // context's camera, set or not, is passed and never read.
+// `acc`: the accumulate that folds each chunk (plain, or with moments).
 void render_wavefront(mrt_ctx* c, const mrt_render_args* a, const uint32_t* pixlist_d, uint32_t n_pix,
                       uint32_t spp_chunk, const ViewTable& views, const RayTable& rays, float* d_rgb, uint32_t* d_b,
-                      hipStream_t st) {
+                      hipStream_t st, const Accum& acc = Accum{}) {
   const bool count = (a->flags & MRT_RENDER_COUNTERS) != 0;
   const bool simple = (a->flags & MRT_RENDER_SIMPLE_TRACE) != 0;
   plan_buffers(c, n_pix, spp_chunk, true);
@@ -880,7 +891,7 @@ void render_wavefront(mrt_ctx* c, const mrt_render_args* a, const uint32_t* pixl
     run_queues(c, rp, p, stamps);
     join_queues(c, st);
     stamps.keep();
-    accumulate(c, rp, d_rgb, d_b, st);
+    accumulate(c, rp, d_rgb, d_b, st, acc);
     HIP_CHECK(hipEventRecord(c->acc_done, st));  // the slab is free again after this
   }
 }
@@ -988,6 +999,59 @@ static void render_rays_device(mrt_ctx* c, const mrt_path_ray* d_rays, uint32_t 
                    d_rgb, d_b, st);
 }
 
+// mrt_render_adaptive_device: the rounds of the adaptive rule around the
+// wavefront loop (massrt.h states the rule, host/adaptive.h its arithmetic).
+// Round r is one render_wavefront over the open tiles' pixel list with the
+// round's sample base and the moment-carrying accumulate: plan_buffers, the
+// queues and the drain are a frame's. Behind it on `st` the open tiles are
+// evaluated (k_adaptive_tiles) and the survivors' pixels compacted into the
+// next list (adaptive_compact), whose length the host waits for: one word per
+// round. So the call returns when its last kernel has ended.
+static void render_adaptive_device(mrt_ctx* c, const mrt_render_args* a, const mrt_adaptive_params* prm, float* d_rgb,
+                                   uint32_t* d_b, float* d_mom, uint32_t* d_smp, mrt_adaptive_report* report,
+                                   hipStream_t st) {
+  if (!a) throw ApiError{MRT_ERR_INVALID, "null render args"};
+  if (!d_rgb || !d_b || !d_mom || !d_smp) throw ApiError{MRT_ERR_INVALID, "null accumulation buffer"};
+  if (const char* why = adapt_render_error(prm, a->spp_begin, a->spp_count, a->flags))
+    throw ApiError{MRT_ERR_INVALID, why};
+  check_render_args(c, a);
+  check_render_flags(c, a);
+  const uint32_t sc = a->shard_count ? a->shard_count : 1;
+  const AdaptFrame f = adaptive_frame(c, a->width, a->height, a->shard_index, sc);
+  if (report) *report = mrt_adaptive_report{};
+  const uint32_t cap = a->spp_count;
+  if (cap == 0 || a->max_depth == 0 || f.n_tiles == 0) return;  // nothing to add
+  auto pl = pixlist(c, a->width, a->height, a->shard_index, sc);
+  const uint32_t n_shard = pl.second;
+  adaptive_scratch(c, f.n_tiles, n_shard);
+  HIP_CHECK(hipMemsetAsync(c->ad_open.p, 1, f.n_tiles, st));  // every tile starts in the running
+  const float tau2 = adapt_tau2(prm->threshold);
+  const uint32_t* list = pl.first;
+  uint32_t n_pix = n_shard, done = 0, round = 0;
+  uint64_t samples = 0;
+  AdaptWord w{n_shard, f.n_tiles};
+  for (;; ++round) {
+    const uint32_t cnt = adapt_round_count(*prm, cap, round, done);
+    if (cnt) {
+      mrt_render_args ra = *a;
+      ra.spp_begin = a->spp_begin + done;
+      ra.spp_count = cnt;
+      render_wavefront(c, &ra, list, n_pix, first_chunk(cnt, c->tun.results_max, n_pix), ViewTable{}, RayTable{},
+                       d_rgb, d_b, st, Accum{d_mom, d_smp});
+      samples += (uint64_t)n_pix * cnt;
+      done += cnt;
+    }
+    adaptive_evaluate(f, d_mom, d_smp, tau2, prm->floor, c->ad_open.p, true, nullptr, st);
+    uint32_t* next = c->ad_list[round & 1].p;
+    w = adaptive_compact(c, f, next, n_shard, round, st);
+    list = next;
+    n_pix = w.pixels;
+    if (!adapt_goes_on(w.tiles, done, cap)) break;
+  }
+  mark_ctx_busy(c, st);
+  if (report) *report = mrt_adaptive_report{round + 1, done, f.n_tiles, w.tiles, samples};
+}
+
 // Kernel timing of renders flagged MRT_RENDER_TIME_KERNELS, resolved when the
 // stats are read (a timed render does not wait for its queue set's drain).
 void resolve_kernel_timing(mrt_ctx* c) {
@@ -1083,6 +1147,44 @@ int mrt_render_rays_device(mrt_ctx* c, const mrt_path_ray* d_rays, uint32_t n_ra
     check_rays_args(c, d_rays, n_rays, spp_begin, spp_count, flags, d_rgb, d_b, false);
     render_rays_device(c, d_rays, n_rays, seed, spp_begin, spp_count, max_depth, flags, d_rgb, d_b,
                        (hipStream_t)stream);  // NULL: the null stream
+  });
+}
+
+int mrt_render_adaptive_device(mrt_ctx* c, const mrt_render_args* a, const mrt_adaptive_params* params, float* d_rgb,
+                               uint32_t* d_b, float* d_moments, uint32_t* d_samples, mrt_adaptive_report* report,
+                               void* stream) {
+  MRT_DEV0(c, mrt_render_adaptive_device(c, a, params, d_rgb, d_b, d_moments, d_samples, report, stream));
+  return guarded(c, [&] {
+    render_adaptive_device(c, a, params, d_rgb, d_b, d_moments, d_samples, report,
+                           (hipStream_t)stream);  // NULL: the null stream
+  });
+}
+
+int mrt_render_adaptive(mrt_ctx* c, const mrt_render_args* a, const mrt_adaptive_params* params, float* rgb,
+                        uint32_t* bounces, float* moments, uint32_t* samples, mrt_adaptive_report* report) {
+  MRT_DEV0(c, mrt_render_adaptive(c, a, params, rgb, bounces, moments, samples, report));
+  return guarded(c, [&] {
+    if (!a || !rgb || !bounces || !moments || !samples) throw ApiError{MRT_ERR_INVALID, "null argument"};
+    if (const char* why = adapt_render_error(params, a->spp_begin, a->spp_count, a->flags))
+      throw ApiError{MRT_ERR_INVALID, why};
+    check_render_args(c, a);  // before the frame's size is trusted
+    const size_t np = (size_t)a->width * a->height;
+    HIP_CHECK(c->d_acc_rgb.reserve(np * 3));
+    HIP_CHECK(c->d_acc_b.reserve(np));
+    HIP_CHECK(c->d_acc_mom.reserve(np * 2));
+    HIP_CHECK(c->d_acc_n.reserve(np));
+    float *d_rgb = c->d_acc_rgb.p, *d_mom = c->d_acc_mom.p;
+    uint32_t *d_b = c->d_acc_b.p, *d_n = c->d_acc_n.p;
+    HIP_CHECK(hipMemcpyAsync(d_rgb, rgb, np * 12, hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(hipMemcpyAsync(d_b, bounces, np * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(hipMemcpyAsync(d_mom, moments, np * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(hipMemcpyAsync(d_n, samples, np * 4, hipMemcpyHostToDevice, c->stream));
+    render_adaptive_device(c, a, params, d_rgb, d_b, d_mom, d_n, report, c->stream);
+    HIP_CHECK(hipMemcpyAsync(rgb, d_rgb, np * 12, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipMemcpyAsync(bounces, d_b, np * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipMemcpyAsync(moments, d_mom, np * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipMemcpyAsync(samples, d_n, np * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
   });
 }
 

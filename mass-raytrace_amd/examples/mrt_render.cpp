@@ -4,7 +4,7 @@
 // passes of 1 spp into the accumulation buffers, tonemap, write PNGs
 // (<out>.png, <out>_depth.png, _albedo, _normal and _denoise).
 //
-//   mrt_render [--orbit N] <scene> <width> <height> <passes> <out.png> [asset_dir] [device]
+//   mrt_render [--orbit N | --pano W H | --adaptive T] <scene> <width> <height> <passes> <out.png> [asset_dir] [device]
 //
 // --orbit N: the reference's EXPORT_FRAMES loop (main.rs:104-141) for a world
 // that does not change: N cameras on a circle around the built-in camera's
@@ -18,6 +18,12 @@
 // the command line are not used). The rays are built here on the host, one
 // per pixel through its centre, key = the pixel, skip = 0; host buffers, then
 // mrt_tonemap and mrt_write_png.
+//
+// --adaptive T: <passes> is a cap, not a count: mrt_render_adaptive samples every
+// 8x8 tile in rounds until its error estimate is below T of its brightness
+// (the library's default minimum, step and floor) or the cap is spent. Writes
+// the resolved frame to <out.png> and the sample map to <out>_samples.png
+// (white: the tiles that took the most samples).
 //
 // Prints one line: scene, size, passes, render seconds, Msamples/s.
 #include <chrono>
@@ -88,8 +94,14 @@ static std::vector<mrt_path_ray> pano_rays(const float* from, uint32_t W, uint32
 
 int main(int argc, char** argv) {
   uint32_t orbit = 0, pano_w = 0, pano_h = 0;
+  float adaptive = -1.0f;
   for (int i = 1; i + 1 < argc; ++i)
-    if (!std::strcmp(argv[i], "--orbit")) {
+    if (!std::strcmp(argv[i], "--adaptive")) {
+      adaptive = (float)std::atof(argv[i + 1]);
+      for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+      argc -= 2;
+      break;
+    } else if (!std::strcmp(argv[i], "--orbit")) {
       orbit = (uint32_t)std::atoi(argv[i + 1]);
       for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
       argc -= 2;
@@ -103,7 +115,7 @@ int main(int argc, char** argv) {
     }
   if (argc < 6) {
     std::fprintf(stderr,
-                 "usage: %s [--orbit N | --pano W H] <scene> <width> <height> <passes> <out.png> [asset_dir] [device]\n",
+                 "usage: %s [--orbit N | --pano W H | --adaptive T] <scene> <width> <height> <passes> <out.png> [asset_dir] [device]\n",
                  argv[0]);
     return 2;
   }
@@ -198,6 +210,37 @@ int main(int argc, char** argv) {
     }
     std::printf("%s %ux%u views=%u passes=%u render_s=%.3f msamples_per_s=%.1f\n", scene.c_str(), W, H, orbit, passes,
                 secs, (double)n * orbit * passes / secs / 1e6);
+    mrt_destroy(ctx);
+    return 0;
+  }
+  if (adaptive >= 0.0f) {
+    mrt_builder_free(b);
+    std::vector<float> rgb(n * 3, 0.0f), moments(n * 2, 0.0f), resolved(n * 3);
+    std::vector<uint32_t> bounces(n, 0), samples(n, 0);
+    std::vector<uint8_t> bytes(n * 3);
+    mrt_adaptive_params prm;
+    mrt_adaptive_default_params(&prm);
+    prm.threshold = adaptive;
+    if (prm.min_spp > passes) prm.min_spp = passes;
+    mrt_adaptive_report rep;
+    const auto t0 = std::chrono::steady_clock::now();
+    mrt_render_args a{W, H, 0, passes, 1, 50, 0, 1, 0};
+    if (mrt_render_adaptive(ctx, &a, &prm, rgb.data(), bounces.data(), moments.data(), samples.data(), &rep) != MRT_OK)
+      return fail("mrt_render_adaptive", ctx);
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (mrt_adaptive_resolve(ctx, W, H, rgb.data(), samples.data(), resolved.data()) != MRT_OK)
+      return fail("mrt_adaptive_resolve", ctx);
+    const size_t dot = out.rfind('.');
+    const std::string map = (dot == std::string::npos ? out : out.substr(0, dot)) + "_samples.png";
+    // the resolved means take Default's bytes with passes = 1; the sample map is the Depth view of the counts
+    if (mrt_tonemap(ctx, W, H, resolved.data(), samples.data(), 1, MRT_DISPLAY_DEFAULT, bytes.data()) != MRT_OK ||
+        mrt_write_png(out.c_str(), W, H, bytes.data()) != MRT_OK ||
+        mrt_tonemap(ctx, W, H, resolved.data(), samples.data(), 1, MRT_DISPLAY_DEPTH, bytes.data()) != MRT_OK ||
+        mrt_write_png(map.c_str(), W, H, bytes.data()) != MRT_OK)
+      return fail("export", ctx);
+    std::printf("%s %ux%u adaptive=%g cap=%u rounds=%u mean_spp=%.1f tiles_open=%u/%u render_s=%.3f msamples_per_s=%.1f\n",
+                scene.c_str(), W, H, adaptive, passes, rep.rounds, (double)rep.samples / (double)n, rep.tiles_open,
+                rep.tiles, secs, (double)rep.samples / secs / 1e6);
     mrt_destroy(ctx);
     return 0;
   }

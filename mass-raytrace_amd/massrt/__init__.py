@@ -215,6 +215,23 @@ class MrtDenoiseParams(C.Structure):
                 "sigma_albedo": float(self.sigma_albedo), "sigma_normal": float(self.sigma_normal)}
 
 
+class MrtAdaptiveParams(C.Structure):
+    """The rule of Context.render_adaptive (mrt_adaptive_params)."""
+    _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("threshold", C.c_float), ("floor", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {"min_spp": int(self.min_spp), "step_spp": int(self.step_spp), "threshold": float(self.threshold),
+                "floor": float(self.floor)}
+
+
+class MrtAdaptiveReport(C.Structure):
+    _fields_ = [("rounds", C.c_uint32), ("spp_reached", C.c_uint32), ("tiles", C.c_uint32),
+                ("tiles_open", C.c_uint32), ("samples", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
 GATHER_AUTO, GATHER_PEER, GATHER_RCCL = 0, 1, 2
 TRAVERSAL_AUTO, TRAVERSAL_REFERENCE, TRAVERSAL_NEAR_FIRST = -1, 0, 1
 
@@ -282,6 +299,8 @@ EXPORTED_SYMBOLS = [
     "mrt_builder_volume_targets",
     "mrt_render_views", "mrt_render_views_device",
     "mrt_render_rays", "mrt_render_rays_device", "mrt_path_stream", "mrt_camera_rays",
+    "mrt_adaptive_default_params", "mrt_render_adaptive", "mrt_render_adaptive_device", "mrt_adaptive_tiles",
+    "mrt_adaptive_tiles_device", "mrt_adaptive_resolve", "mrt_adaptive_resolve_device",
 ]
 
 _lib = None
@@ -396,6 +415,16 @@ def lib() -> C.CDLL:
         "mrt_path_stream": (I, [U64, U32, U32, U32, C.POINTER(C.c_uint64), fp]),
         "mrt_camera_rays": (I, [C.POINTER(MrtCamera), U32, U32, C.POINTER(C.c_uint32), U32, U64, U32,
                                 C.POINTER(MrtPathRay)]),
+        "mrt_adaptive_default_params": (I, [C.POINTER(MrtAdaptiveParams)]),
+        "mrt_render_adaptive": (I, [P, C.POINTER(MrtRenderArgs), C.POINTER(MrtAdaptiveParams), fp,
+                                    C.POINTER(C.c_uint32), fp, C.POINTER(C.c_uint32), C.POINTER(MrtAdaptiveReport)]),
+        "mrt_render_adaptive_device": (I, [P, C.POINTER(MrtRenderArgs), C.POINTER(MrtAdaptiveParams), P, P, P, P,
+                                           C.POINTER(MrtAdaptiveReport), P]),
+        "mrt_adaptive_tiles": (I, [U32, U32, U32, U32, fp, C.POINTER(C.c_uint32), C.POINTER(MrtAdaptiveParams),
+                                   C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]),
+        "mrt_adaptive_tiles_device": (I, [P, U32, U32, U32, U32, P, P, C.POINTER(MrtAdaptiveParams), P, P, P]),
+        "mrt_adaptive_resolve": (I, [P, U32, U32, fp, C.POINTER(C.c_uint32), fp]),
+        "mrt_adaptive_resolve_device": (I, [P, U32, U32, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -838,6 +867,69 @@ class Context:
                                                  max_depth, flags, C.c_void_p(d_rgb), C.c_void_p(d_bounces),
                                                  C.c_void_p(stream or 0)))
 
+    def render_adaptive(self, width, height, spp_begin=0, spp_count=64, seed=1, max_depth=MAX_DEPTH, shard_index=0,
+                        shard_count=1, flags=0, accum=None, **params):
+        """mrt_render_adaptive: every 8x8 tile of the shard sampled in rounds
+        until its error is met or spp_count samples per pixel (the cap) are
+        spent (massrt.h states the rule). params: min_spp, step_spp, threshold,
+        floor (adaptive_defaults()). Returns (rgb float32 [H*W*3], bounces
+        uint32 [H*W], moments float32 [H*W*2], samples uint32 [H*W], report
+        dict); accum=(rgb, bounces, moments, samples) continues an estimate
+        in place."""
+        n = width * height
+        if accum is None:
+            accum = (np.zeros(n * 3, np.float32), np.zeros(n, np.uint32), np.zeros(n * 2, np.float32),
+                     np.zeros(n, np.uint32))
+        rgb, b, mom, smp = accum
+        for a, dt in ((rgb, np.float32), (b, np.uint32), (mom, np.float32), (smp, np.uint32)):
+            if a.dtype != dt or not a.flags.c_contiguous:
+                raise ValueError("render_adaptive accumulates in place: contiguous float32 and uint32 buffers")
+        a = self.args(width, height, spp_begin, spp_count, seed, max_depth, shard_index, shard_count, flags=flags)
+        p = adaptive_params(**params)
+        rep = MrtAdaptiveReport()
+        u32 = C.POINTER(C.c_uint32)
+        self._check(lib().mrt_render_adaptive(self.h, C.byref(a), C.byref(p), _fptr(rgb), b.ctypes.data_as(u32),
+                                              _fptr(mom), smp.ctypes.data_as(u32), C.byref(rep)))
+        return rgb, b, mom, smp, rep.as_dict()
+
+    def render_adaptive_device(self, args: MrtRenderArgs, d_rgb: int, d_bounces: int, d_moments: int, d_samples: int,
+                               stream: int | None = None, **params) -> dict:
+        """mrt_render_adaptive_device: device buffers, ordered on `stream`;
+        returns the report when the render has ended."""
+        p = adaptive_params(**params)
+        rep = MrtAdaptiveReport()
+        self._check(lib().mrt_render_adaptive_device(self.h, C.byref(args), C.byref(p), C.c_void_p(d_rgb),
+                                                     C.c_void_p(d_bounces), C.c_void_p(d_moments),
+                                                     C.c_void_p(d_samples), C.byref(rep), C.c_void_p(stream or 0)))
+        return rep.as_dict()
+
+    def adaptive_tiles_device(self, width, height, d_moments: int, d_samples: int, d_open: int,
+                              d_n_open: int | None = None, shard_index=0, shard_count=1, stream: int | None = None,
+                              **params):
+        """mrt_adaptive_tiles_device: the decision alone from device buffers,
+        one byte per tile of the shard into d_open (1 = open)."""
+        p = adaptive_params(**params)
+        self._check(lib().mrt_adaptive_tiles_device(self.h, width, height, shard_index, shard_count,
+                                                    C.c_void_p(d_moments), C.c_void_p(d_samples), C.byref(p),
+                                                    C.c_void_p(d_open), C.c_void_p(d_n_open or 0),
+                                                    C.c_void_p(stream or 0)))
+
+    def adaptive_resolve(self, width, height, rgb, samples) -> np.ndarray:
+        """mrt_adaptive_resolve: sums / per-pixel sample count, float32 [H*W*3]
+        (zeros where the count is 0). The bytes: tonemap(.., passes=1,
+        DISPLAY_DEFAULT) of the result."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32).reshape(-1)
+        smp = np.ascontiguousarray(samples, dtype=np.uint32).reshape(-1)
+        out = np.empty(width * height * 3, dtype=np.float32)
+        self._check(lib().mrt_adaptive_resolve(self.h, width, height, _fptr(rgb),
+                                               smp.ctypes.data_as(C.POINTER(C.c_uint32)), _fptr(out)))
+        return out
+
+    def adaptive_resolve_device(self, width, height, d_rgb: int, d_samples: int, d_out: int,
+                                stream: int | None = None):
+        self._check(lib().mrt_adaptive_resolve_device(self.h, width, height, C.c_void_p(d_rgb), C.c_void_p(d_samples),
+                                                      C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
     def trace_rays(self, rays: np.ndarray, t_min=0.001, t_max=float("inf")):
         r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
         n = r.shape[0]
@@ -1016,6 +1108,50 @@ def denoise_params(**params) -> MrtDenoiseParams:
     d.update(params)
     return MrtDenoiseParams(int(d["iterations"]), float(d["sigma_color"]), float(d["sigma_albedo"]),
                             float(d["sigma_normal"]))
+
+
+def adaptive_defaults() -> dict:
+    """mrt_adaptive_default_params: min_spp, step_spp, threshold, floor."""
+    p = MrtAdaptiveParams()
+    if lib().mrt_adaptive_default_params(C.byref(p)) != 0:
+        raise MassrtError(lib().mrt_global_last_error().decode())
+    return p.as_dict()
+
+
+def adaptive_params(**params) -> MrtAdaptiveParams:
+    """The defaults with `params` over them; an unknown name raises TypeError."""
+    d = adaptive_defaults()
+    unknown = sorted(set(params) - set(d))
+    if unknown:
+        raise TypeError(f"unknown adaptive parameter(s) {unknown}; there are {sorted(d)}")
+    d.update(params)
+    return MrtAdaptiveParams(int(d["min_spp"]), int(d["step_spp"]), float(d["threshold"]), float(d["floor"]))
+
+
+def adaptive_tile_count(width: int, height: int, shard_index: int = 0, shard_count: int = 1) -> int:
+    """Tiles (MRT_TILE x MRT_TILE) shard `shard_index` of `shard_count` owns: frame tiles t with t % count == index."""
+    t = ((width + 7) // 8) * ((height + 7) // 8)
+    return len(range(shard_index, t, max(shard_count, 1)))
+
+
+def adaptive_tiles(width, height, moments, samples, shard_index=0, shard_count=1, **params) -> np.ndarray:
+    """mrt_adaptive_tiles: the decision alone (host only): one byte per tile of
+    the shard in shard order, 1 = open; only threshold and floor are read."""
+    mom = np.ascontiguousarray(moments, dtype=np.float32).reshape(-1)
+    smp = np.ascontiguousarray(samples, dtype=np.uint32).reshape(-1)
+    if mom.size != 2 * width * height or smp.size != width * height:
+        raise ValueError("adaptive_tiles: moments are W*H*2 floats and samples W*H counts")
+    p = adaptive_params(**params)
+    out = np.zeros(max(adaptive_tile_count(width, height, shard_index, shard_count), 1), dtype=np.uint8)
+    n = C.c_uint32()
+    rc = lib().mrt_adaptive_tiles(width, height, shard_index, shard_count, _fptr(mom),
+                                  smp.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(p),
+                                  out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(n))
+    if rc != 0:
+        raise MassrtError(lib().mrt_global_last_error().decode())
+    out = out[: adaptive_tile_count(width, height, shard_index, shard_count)]
+    assert int(out.sum()) == n.value
+    return out
 
 
 def gamma_thresholds() -> np.ndarray:
