@@ -236,9 +236,6 @@ std::vector<uint32_t> shard_pixel_list(uint32_t W, uint32_t H, uint32_t si, uint
 std::pair<uint32_t*, uint32_t> pixlist(mrt_ctx* c, uint32_t W, uint32_t H, uint32_t si, uint32_t sc,
                                        uint32_t n_views = 0);
 void mark_ctx_busy(mrt_ctx* c, hipStream_t st);
-void render_device(mrt_ctx* c, const mrt_render_args* a, float* d_rgb, uint32_t* d_b, hipStream_t st);
-void render_views_device(mrt_ctx* c, const mrt_render_args* a, const mrt_view* views, uint32_t n_views, float* d_rgb,
-                         uint32_t* d_b, hipStream_t st);
 mrt::DevCamera dev_camera(const mrt_camera& cam);
 void resolve_kernel_timing(mrt_ctx* c);
 

@@ -79,7 +79,7 @@ struct alignas(16) DevView {
 };
 static_assert(sizeof(DevView) == 96 && offsetof(DevView, seed) == 80, "DevView: 96 B, the seed on an 8-B boundary");
 
-// Where the view variants of the generation kernels take the camera from: the
+// Where k_generate<ViewTable> / k_refill<ViewTable> take the camera from: the
 // render's pixel list then holds global pixels P = v pix_per_view + p
 // (loop.h view_split). Its own kernel argument; RenderParams stays as it is.
 struct ViewTable {
@@ -89,7 +89,7 @@ struct ViewTable {
   uint32_t* dbg;  // MRT_IDX's record (DevScene::dbg)
 };
 
-// Where the ray variants of the generation kernels take a path's start from
+// Where k_generate<RayTable> / k_refill<RayTable> take a path's start from
 // (mrt_render_rays): work item g = i spp + s is sample s of entry i (loop.h
 // ray_work), its result goes to list position i. Entries are 32 B, read as two
 // 16-byte loads: the table is 16-byte aligned. The kernels only read it.

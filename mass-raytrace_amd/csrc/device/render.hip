@@ -6,14 +6,15 @@
 //   k_trace : closest hit of every active ray (World::intersect; trace.hip) [k2]
 //   k_shade : emit/scatter/background, path termination and wave
 //             ballot/prefix-sum compaction of the survivors           [k3,k4]
-//   k_reserve + k_refill : new camera rays (Camera::ray) for the free
-//             slots behind the survivors                              [k1]
+//   k_reserve + k_refill<SRC> : new paths for the free slots behind the
+//             survivors: camera rays (Camera::ray) or a caller's rays [k1]
 // Finished samples are written to a per-(pixel,sample) result slab and folded
 // into the caller's accumulation buffers in sample order by k_accumulate [k5]
 // (Image::merge, main.rs:629-638), so the sums do not depend on scheduling
 // or on how tiles are sharded across GPUs.
 #include <algorithm>
 #include <mutex>
+#include <variant>
 
 #include "ctx.h"
 #include "shade.h"
@@ -104,24 +105,14 @@ __device__ __forceinline__ void gen_path(const CAM& cam, const RenderParams& rp,
   out.rng[i] = rs;
 }
 
-// Initial pool: work items [base, base + n0) into slots [0, n0).
-__global__ __launch_bounds__(kBlock) void k_generate(DevCamera cam, RenderParams rp, PathBufs out, uint32_t base,
+// Initial pool: work items [base, base + n0) into slots [0, n0). SRC: where a
+// path starts (DevCamera, ViewTable or RayTable; with_source chooses).
+template <typename SRC>
+__global__ __launch_bounds__(kBlock) void k_generate(SRC src, RenderParams rp, PathBufs out, uint32_t base,
                                                      uint32_t n0) {
   uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= n0) return;
-  gen_path(cam, rp, out, base + i, i);
-}
-__global__ __launch_bounds__(kBlock) void k_generate_views(ViewTable views, RenderParams rp, PathBufs out,
-                                                           uint32_t base, uint32_t n0) {
-  uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n0) return;
-  gen_path(views, rp, out, base + i, i);
-}
-__global__ __launch_bounds__(kBlock) void k_generate_rays(RayTable rays, RenderParams rp, PathBufs out, uint32_t base,
-                                                          uint32_t n0) {
-  uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n0) return;
-  gen_path(rays, rp, out, base + i, i);
+  gen_path(src, rp, out, base + i, i);
 }
 
 // The identity list of a ray list's render: k_accumulate adds list entry i's
@@ -192,16 +183,9 @@ __device__ __forceinline__ void refill(const CAM& cam, const RenderParams& rp, c
   for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < m; j += gridDim.x * kBlock)
     gen_path(cam, rp, out, base + j, slot + j);
 }
-__global__ __launch_bounds__(kBlock) void k_refill(DevCamera cam, RenderParams rp, PathBufs out, const Ctrl* ctrl) {
-  refill(cam, rp, out, ctrl);
-}
-__global__ __launch_bounds__(kBlock) void k_refill_views(ViewTable views, RenderParams rp, PathBufs out,
-                                                         const Ctrl* ctrl) {
-  refill(views, rp, out, ctrl);
-}
-__global__ __launch_bounds__(kBlock) void k_refill_rays(RayTable rays, RenderParams rp, PathBufs out,
-                                                        const Ctrl* ctrl) {
-  refill(rays, rp, out, ctrl);
+template <typename SRC>
+__global__ __launch_bounds__(kBlock) void k_refill(SRC src, RenderParams rp, PathBufs out, const Ctrl* ctrl) {
+  refill(src, rp, out, ctrl);
 }
 
 // k_shade only shades and compacts: new camera rays go in behind the
@@ -532,34 +516,35 @@ void launch_finish(mrt_ctx* c, int qi, uint32_t cur, const RenderParams& rp, boo
   HIP_CHECK(hipGetLastError());
 }
 
-// The accumulate a wavefront render folds its slab with: plain k_accumulate,
-// or (moments set) adaptive.hip's, which adds the moments and counts of
-// mrt_render_adaptive beside the same sums.
+// The accumulation buffers a render adds to, on the device or (Staging) the
+// caller's on the host. moments set: mrt_render_adaptive's, whose accumulate
+// (adaptive.hip) adds the moments and counts beside the same sums.
 struct Accum {
+  float* rgb;
+  uint32_t* bounces;
   float* moments = nullptr;
   uint32_t* samples = nullptr;
 };
 
-// Folds a chunk's results slab into the caller's accumulation buffers on `st`
+// Folds a chunk's results slab into the accumulation buffers on `st`
 // (k_accumulate: in sample order).
-void accumulate(mrt_ctx* c, const RenderParams& rp, float* d_rgb, uint32_t* d_b, hipStream_t st,
-                const Accum& acc = Accum{}) {
-  if (acc.moments) return accumulate_moments(c, rp, d_rgb, d_b, acc.moments, acc.samples, st);
+void accumulate(mrt_ctx* c, const RenderParams& rp, const Accum& acc, hipStream_t st) {
+  if (acc.moments) return accumulate_moments(c, rp, acc.rgb, acc.bounces, acc.moments, acc.samples, st);
   hipLaunchKernelGGL(k_accumulate, dim3((rp.n_pix + kAccPix - 1) / kAccPix), dim3(kBlock), 0, st,
-                     (const float4*)c->results.p, rp.n_pix, rp.spp, rp.pixlist, d_rgb, d_b);
+                     (const float4*)c->results.p, rp.n_pix, rp.spp, rp.pixlist, acc.rgb, acc.bounces);
   HIP_CHECK(hipGetLastError());
 }
 
 // The fused path loop: one k_render launch + one k_accumulate per chunk.
-void render_fused(mrt_ctx* c, const mrt_render_args* a, const uint32_t* pixlist_d, uint32_t n_pix, uint32_t spp_chunk,
-                  float* d_rgb, uint32_t* d_b, hipStream_t st) {
+void render_fused(mrt_ctx* c, const mrt_render_args* a, const uint32_t* pixlist_d, uint32_t n_pix, const Accum& acc,
+                  hipStream_t st) {
   const bool count = (a->flags & MRT_RENDER_COUNTERS) != 0;
   const bool timing = (a->flags & MRT_RENDER_TIME_KERNELS) != 0;
+  uint32_t spp_chunk = first_chunk(a->spp_count, c->tun.results_max, n_pix);
   plan_buffers(c, n_pix, spp_chunk, false);
   wait_queues(c, st);
   for (uint32_t done = 0; done < a->spp_count; done += spp_chunk) {
     const uint32_t cs = std::min(spp_chunk, a->spp_count - done);
-    if (a->max_depth == 0) continue;  // trace(ray, 0) returns (0, 0): nothing to add
     const RenderParams rp = chunk_params(c, a, pixlist_d, n_pix, done, cs, 0);
     const Ctrl init = ctrl_init(0);
     HIP_CHECK(hipMemcpyAsync(c->q[0].ctrl.p, &init, sizeof(Ctrl), hipMemcpyHostToDevice, st));
@@ -579,7 +564,7 @@ void render_fused(mrt_ctx* c, const mrt_render_args* a, const uint32_t* pixlist_
       c->kstats.trace_launches++;
       c->kstats.iterations++;
     }
-    accumulate(c, rp, d_rgb, d_b, st);
+    accumulate(c, rp, acc, st);
   }
   mark_ctx_busy(c, st);
 }
@@ -697,26 +682,43 @@ struct Stamps {
   }
 };
 
+// Where the paths of a render start, exactly one of: the context's camera, a
+// batch of views (the cameras from the table), a caller's ray list (no camera
+// at all). A new source is a table struct, a gen_work overload and one
+// alternative here.
+using Source = std::variant<DevCamera, ViewTable, RayTable>;
+
+// The one place a source becomes a template argument: f(src) with a copy of
+// the alternative, so k_generate / k_refill <decltype(src)> follow from it.
+template <typename F>
+void with_source(const Source& s, F&& f) {
+  std::visit(f, s);
+}
+
 // What the chunks of one wavefront render share.
 struct Pass {
   bool count, simple;
   uint32_t finish_paths;  // drain hand-off threshold (0: never)
   ShadeFn shade;
-  ViewTable views;  // views.views != nullptr: a batch of views, the cameras from this table (the context's otherwise)
-  RayTable rays;    // rays.rays != nullptr: a caller's ray list, the path starts from this table (no camera at all)
+  Source src;
 };
+
+// What every render needs, of a frame or of a ray list (with loop.h samples_fit).
+void check_scene(const mrt_ctx* c) {
+  if (!c->has_scene) throw ApiError{MRT_ERR_STATE, "no scene uploaded"};
+}
 
 // The argument and state errors of a render, before anything is enqueued.
 // (A batch of views brings its own cameras: need_camera false.)
 void check_render_args(const mrt_ctx* c, const mrt_render_args* a, bool need_camera = true) {
   if (!a) throw ApiError{MRT_ERR_INVALID, "null render args"};
-  if (!c->has_scene) throw ApiError{MRT_ERR_STATE, "no scene uploaded"};
+  check_scene(c);
   if (need_camera && !c->has_camera) throw ApiError{MRT_ERR_STATE, "no camera set"};
   if (a->width == 0 || a->height == 0) throw ApiError{MRT_ERR_INVALID, "empty image"};
   if ((uint64_t)a->width * a->height >= (1ull << 32)) throw ApiError{MRT_ERR_INVALID, "image too large"};
   if (a->shard_index >= (a->shard_count ? a->shard_count : 1))
     throw ApiError{MRT_ERR_INVALID, "shard_index >= shard_count"};
-  if ((uint64_t)a->spp_begin + a->spp_count > 0xFFFFFFFFull) throw ApiError{MRT_ERR_INVALID, "sample index overflow"};
+  if (!samples_fit(a->spp_begin, a->spp_count)) throw ApiError{MRT_ERR_INVALID, "sample index overflow"};
 }
 
 // What the scene rules out for the render's flags.
@@ -751,12 +753,9 @@ void fork_queues(mrt_ctx* c, const RenderParams& rp, const Pass& p) {
     HIP_CHECK(hipMemcpyAsync(q.ctrl.p, &init, sizeof(Ctrl), hipMemcpyHostToDevice, q.stream));
     if (nk) {
       const dim3 grid((nk + kBlock - 1) / kBlock);
-      if (p.rays.rays)
-        hipLaunchKernelGGL(k_generate_rays, grid, dim3(kBlock), 0, q.stream, p.rays, rp, q.bufs[0], base, nk);
-      else if (p.views.views)
-        hipLaunchKernelGGL(k_generate_views, grid, dim3(kBlock), 0, q.stream, p.views, rp, q.bufs[0], base, nk);
-      else
-        hipLaunchKernelGGL(k_generate, grid, dim3(kBlock), 0, q.stream, c->cam, rp, q.bufs[0], base, nk);
+      with_source(p.src, [&](auto src) {
+        hipLaunchKernelGGL(k_generate<decltype(src)>, grid, dim3(kBlock), 0, q.stream, src, rp, q.bufs[0], base, nk);
+      });
       HIP_CHECK(hipGetLastError());
     }
     base += nk;
@@ -779,15 +778,10 @@ void enqueue_batch(mrt_ctx* c, Queue& q, QueueLoop& L, const RenderParams& rp, c
     HIP_CHECK(hipGetLastError());
     if (!L.exhausted || rp.shade_bin == 2) {  // new paths behind the survivors (shade_bin 2: and the pool's ends joined)
       hipLaunchKernelGGL(k_reserve, dim3(1), dim3(64), 0, q.stream, q.ctrl.p, cur, c->work.p, rp.G, rp.pool_cap);
-      if (p.rays.rays)
-        hipLaunchKernelGGL(k_refill_rays, dim3(c->refill_grid), dim3(kBlock), 0, q.stream, p.rays, rp,
+      with_source(p.src, [&](auto src) {
+        hipLaunchKernelGGL(k_refill<decltype(src)>, dim3(c->refill_grid), dim3(kBlock), 0, q.stream, src, rp,
                            q.bufs[cur ^ 1], (const Ctrl*)q.ctrl.p);
-      else if (p.views.views)
-        hipLaunchKernelGGL(k_refill_views, dim3(c->refill_grid), dim3(kBlock), 0, q.stream, p.views, rp,
-                           q.bufs[cur ^ 1], (const Ctrl*)q.ctrl.p);
-      else
-        hipLaunchKernelGGL(k_refill, dim3(c->refill_grid), dim3(kBlock), 0, q.stream, c->cam, rp, q.bufs[cur ^ 1],
-                           (const Ctrl*)q.ctrl.p);
+      });
       HIP_CHECK(hipGetLastError());
     }
     const hipEvent_t m2 = t.stamp(q.stream);
@@ -855,24 +849,20 @@ void join_queues(mrt_ctx* c, hipStream_t st) {
   }
 }
 
-}  // namespace
-
-namespace {
-
 // The wavefront loop over a pixel list, every step from plan_buffers on: what
-// a render of the context's camera, a render of a batch of views
-// (views.views != nullptr; the list then holds global pixels) and a render of
-// a caller's ray list (rays.rays != nullptr; the list is the identity, width
-// and height are not read) share.
+// a render of the context's camera, a render of a batch of views (a
+// ViewTable; the list then holds global pixels) and a render of a caller's
+// ray list (a RayTable; the list is the identity, width and height are not
+// read) share.
 // The drain hand-off needs no camera under either table: launch_finish's
 // kernel only adopts live paths (ADOPT: gen_work is not in it), so the
 // context's camera, set or not, is passed and never read.
 // `acc`: the accumulate that folds each chunk (plain, or with moments).
 void render_wavefront(mrt_ctx* c, const mrt_render_args* a, const uint32_t* pixlist_d, uint32_t n_pix,
-                      uint32_t spp_chunk, const ViewTable& views, const RayTable& rays, float* d_rgb, uint32_t* d_b,
-                      hipStream_t st, const Accum& acc = Accum{}) {
+                      const Source& src, const Accum& acc, hipStream_t st) {
   const bool count = (a->flags & MRT_RENDER_COUNTERS) != 0;
   const bool simple = (a->flags & MRT_RENDER_SIMPLE_TRACE) != 0;
+  uint32_t spp_chunk = first_chunk(a->spp_count, c->tun.results_max, n_pix);
   plan_buffers(c, n_pix, spp_chunk, true);
   Stamps stamps{c, (a->flags & MRT_RENDER_TIME_KERNELS) != 0};
   if (stamps.timing && c->pend_marks.size() + c->pend_fin.size() > kMaxPendingMarks) resolve_kernel_timing(c);
@@ -881,46 +871,56 @@ void render_wavefront(mrt_ctx* c, const mrt_render_args* a, const uint32_t* pixl
   // any queue runs (ensure_slots reallocates)
   const bool can_finish = !c->facts.trav_rng && !c->scene_ext && !simple;
   const Pass p{count, simple, can_finish ? c->tun.finish_paths : 0u, shade_kernel(count, c->scene_ext, c->tun.shade_wpe),
-               views, rays};
+               src};
   if (p.finish_paths) ensure_slots(c, (size_t)finish_grid(c, count) * kBlock * kMaxQueues);
   for (uint32_t done = 0; done < a->spp_count; done += spp_chunk) {
     const uint32_t cs = std::min(spp_chunk, a->spp_count - done);
     const RenderParams rp = chunk_params(c, a, pixlist_d, n_pix, done, cs, (uint32_t)c->q[0].cap);
-    if (a->max_depth == 0) continue;  // trace(ray, 0) returns (0, 0) for every sample: nothing to add
     fork_queues(c, rp, p);
     run_queues(c, rp, p, stamps);
     join_queues(c, st);
     stamps.keep();
-    accumulate(c, rp, d_rgb, d_b, st, acc);
+    accumulate(c, rp, acc, st);
     HIP_CHECK(hipEventRecord(c->acc_done, st));  // the slab is free again after this
   }
 }
 
-}  // namespace
-
-void render_device(mrt_ctx* c, const mrt_render_args* a, float* d_rgb, uint32_t* d_b, hipStream_t st) {
-  check_render_args(c, a);
-  if (a->spp_count == 0) return;
-  auto pl = pixlist(c, a->width, a->height, a->shard_index, a->shard_count ? a->shard_count : 1);
-  const uint32_t n_pix = pl.second;
-  if (n_pix == 0) return;
-  check_render_flags(c, a);
-  const bool simple = (a->flags & MRT_RENDER_SIMPLE_TRACE) != 0;
-  const uint32_t spp_chunk = first_chunk(a->spp_count, c->tun.results_max, n_pix);
-  if ((a->flags & MRT_RENDER_FUSED) && !simple) {
-    render_fused(c, a, pl.first, n_pix, spp_chunk, d_rgb, d_b, st);
-    return;
-  }
-  render_wavefront(c, a, pl.first, n_pix, spp_chunk, ViewTable{}, RayTable{}, d_rgb, d_b, st);
+// Every entry point below is a check_* that throws the call's argument and
+// state errors and enqueues nothing on a stream (it does fetch the pixel list,
+// which the first call for a frame size builds and uploads), and a run_* that
+// does the work; the ABI's host form stages the caller's buffers between them.
+// A check returns the list to work over: the shard's pixels as pixlist gives
+// them, once per view for a batch; empty where the render has nothing to add.
+using Work = std::pair<uint32_t*, uint32_t>;
+Work frame_work(mrt_ctx* c, const mrt_render_args* a, uint32_t n_views = 0) {
+  if (a->spp_count == 0) return Work{};  // no list is built for a render without samples
+  return pixlist(c, a->width, a->height, a->shard_index, a->shard_count ? a->shard_count : 1, n_views);
+}
+Work or_nothing(const mrt_render_args* a, const Work& w) {
+  return nothing_to_add(a->spp_count, a->max_depth, w.second) ? Work{} : w;
 }
 
-// mrt_render_views_device: one wavefront render over the shard's pixels of
+// mrt_render(_device). Kept as it was: without samples or pixels the flags are
+// not looked at; with depth 0 (trace(ray, 0) returns (0, 0)) they are.
+Work check_render(mrt_ctx* c, const mrt_render_args* a) {
+  check_render_args(c, a);
+  const Work w = frame_work(c, a);
+  if (w.second) check_render_flags(c, a);
+  return or_nothing(a, w);
+}
+void run_render(mrt_ctx* c, const mrt_render_args* a, const Work& w, const Accum& acc, hipStream_t st) {
+  if ((a->flags & MRT_RENDER_FUSED) && !(a->flags & MRT_RENDER_SIMPLE_TRACE))
+    render_fused(c, a, w.first, w.second, acc, st);
+  else
+    render_wavefront(c, a, w.first, w.second, c->cam, acc, st);
+}
+
+// mrt_render_views(_device): one wavefront render over the shard's pixels of
 // every view (loop.h view_list), the cameras and seeds from a table on the
 // device. The pool and the results slab are planned for all views at once, so
 // a batch of small frames fills the pool as one large frame does, and drains
 // once per chunk.
-void render_views_device(mrt_ctx* c, const mrt_render_args* a, const mrt_view* views, uint32_t n_views, float* d_rgb,
-                         uint32_t* d_b, hipStream_t st) {
+Work check_views(mrt_ctx* c, const mrt_render_args* a, const mrt_view* views, uint32_t n_views) {
   if (!views || n_views == 0) throw ApiError{MRT_ERR_INVALID, "mrt_render_views: no views"};
   check_render_args(c, a, false);
   if (!views_fit(n_views, a->width, a->height))
@@ -928,11 +928,10 @@ void render_views_device(mrt_ctx* c, const mrt_render_args* a, const mrt_view* v
   if (a->flags & MRT_RENDER_FUSED)
     throw ApiError{MRT_ERR_INVALID, "mrt_render_views: MRT_RENDER_FUSED renders one camera"};
   check_render_flags(c, a);
-  if (a->spp_count == 0) return;
-  auto pl = pixlist(c, a->width, a->height, a->shard_index, a->shard_count ? a->shard_count : 1, n_views);
-  const uint32_t n_pix = pl.second;
-  if (n_pix == 0) return;
-  if (a->max_depth == 0) return;  // trace(ray, 0) returns (0, 0) for every sample: nothing to add
+  return or_nothing(a, frame_work(c, a, n_views));
+}
+void run_views(mrt_ctx* c, const mrt_render_args* a, const Work& w, const mrt_view* views, uint32_t n_views,
+               const Accum& acc, hipStream_t st) {
   // the caller's views are consumed here. The host copy stays with the
   // context: the upload below reads it when queue 0's stream gets there, and
   // by the next batch it has (that batch's host loop read the status of
@@ -951,14 +950,14 @@ void render_views_device(mrt_ctx* c, const mrt_render_args* a, const mrt_view* v
   HIP_CHECK(hipMemcpyAsync(c->views.p, table.data(), (size_t)n_views * sizeof(DevView), hipMemcpyHostToDevice,
                            c->q[0].stream));
   const ViewTable vt{c->views.p, a->width * a->height, n_views, c->dbg.p};
-  render_wavefront(c, a, pl.first, n_pix, first_chunk(a->spp_count, c->tun.results_max, n_pix), vt, RayTable{}, d_rgb,
-                   d_b, st);
+  render_wavefront(c, a, w.first, w.second, vt, acc, st);
 }
 
-// The argument and state errors of a ray list's render, before anything is
-// enqueued; `host`: the table is in host memory and its skips can be read.
-static void check_rays_args(const mrt_ctx* c, const mrt_path_ray* rays, uint32_t n_rays, uint32_t spp_begin,
-                     uint32_t spp_count, uint32_t flags, const void* rgb, const void* bounces, bool host) {
+// mrt_render_rays(_device). `host`: the table is in host memory and its skips
+// can be read; a table on the device can only be looked at from outside.
+// false: nothing to add.
+bool check_rays(const mrt_ctx* c, const mrt_path_ray* rays, uint32_t n_rays, uint32_t spp_begin, uint32_t spp_count,
+                uint32_t max_depth, uint32_t flags, const void* rgb, const void* bounces, bool host) {
   if (!rgb || !bounces) throw ApiError{MRT_ERR_INVALID, "null accumulation buffer"};
   if (!rays || n_rays == 0) throw ApiError{MRT_ERR_INVALID, "mrt_render_rays: no rays"};
   if (flags & (MRT_RENDER_FUSED | MRT_RENDER_SIMPLE_TRACE))
@@ -970,19 +969,19 @@ static void check_rays_args(const mrt_ctx* c, const mrt_path_ray* rays, uint32_t
       throw ApiError{MRT_ERR_INVALID, "mrt_render_rays: entry " + std::to_string(bad) + " has skip " +
                                           std::to_string(rays[bad].skip) + ", above MRT_RAY_SKIP_MAX"};
   }
-  if (!c->has_scene) throw ApiError{MRT_ERR_STATE, "no scene uploaded"};
+  check_scene(c);
+  if (!host && ((uintptr_t)rays & 15u))
+    throw ApiError{MRT_ERR_INVALID, "mrt_render_rays: the device table must be 16-byte aligned"};
+  return !nothing_to_add(spp_count, max_depth, n_rays);
 }
 
-// mrt_render_rays_device: one wavefront render over the work items of a ray
-// list on the device (loop.h ray_work), every step a frame's from plan_buffers
-// on. The queues' generation kernels read the table, which the caller's
-// stream may have just written: queue 0's stream, on which every fork of this
-// render follows, waits for `st` as it stands now.
-static void render_rays_device(mrt_ctx* c, const mrt_path_ray* d_rays, uint32_t n_rays, uint64_t seed, uint32_t spp_begin,
-                        uint32_t spp_count, uint32_t max_depth, uint32_t flags, float* d_rgb, uint32_t* d_b,
-                        hipStream_t st) {
-  if ((uintptr_t)d_rays & 15u) throw ApiError{MRT_ERR_INVALID, "mrt_render_rays: the device table must be 16-byte aligned"};
-  if (spp_count == 0 || max_depth == 0) return;  // trace(ray, 0) returns (0, 0) for every sample: nothing to add
+// One wavefront render over the work items of a ray list on the device
+// (loop.h ray_work), every step a frame's from plan_buffers on. The queues'
+// generation kernels read the table, which the caller's stream may have just
+// written: queue 0's stream, on which every fork of this render follows,
+// waits for `st` as it stands now.
+void run_rays(mrt_ctx* c, const mrt_path_ray* d_rays, uint32_t n_rays, uint64_t seed, uint32_t spp_begin,
+              uint32_t spp_count, uint32_t max_depth, uint32_t flags, const Accum& acc, hipStream_t st) {
   if (c->ray_ids.n < n_rays) {
     if (c->ray_ids.p) HIP_CHECK(hipDeviceSynchronize());  // an earlier render's accumulate may still read the old list
     HIP_CHECK(c->ray_ids.alloc(n_rays));
@@ -994,35 +993,35 @@ static void render_rays_device(mrt_ctx* c, const mrt_path_ray* d_rays, uint32_t 
   HIP_CHECK(hipEventRecord(c->rays_ready, st));
   HIP_CHECK(hipStreamWaitEvent(c->q[0].stream, c->rays_ready, 0));
   const mrt_render_args a{n_rays, 1u, spp_begin, spp_count, seed, max_depth, 0u, 1u, flags};
-  const RayTable rt{d_rays, n_rays, c->dbg.p};
-  render_wavefront(c, &a, c->ray_ids.p, n_rays, first_chunk(spp_count, c->tun.results_max, n_rays), ViewTable{}, rt,
-                   d_rgb, d_b, st);
+  render_wavefront(c, &a, c->ray_ids.p, n_rays, RayTable{d_rays, n_rays, c->dbg.p}, acc, st);
 }
 
-// mrt_render_adaptive_device: the rounds of the adaptive rule around the
-// wavefront loop (massrt.h states the rule, host/adaptive.h its arithmetic).
-// Round r is one render_wavefront over the open tiles' pixel list with the
-// round's sample base and the moment-carrying accumulate: plan_buffers, the
-// queues and the drain are a frame's. Behind it on `st` the open tiles are
-// evaluated (k_adaptive_tiles) and the survivors' pixels compacted into the
-// next list (adaptive_compact), whose length the host waits for: one word per
-// round. So the call returns when its last kernel has ended.
-static void render_adaptive_device(mrt_ctx* c, const mrt_render_args* a, const mrt_adaptive_params* prm, float* d_rgb,
-                                   uint32_t* d_b, float* d_mom, uint32_t* d_smp, mrt_adaptive_report* report,
-                                   hipStream_t st) {
-  if (!a) throw ApiError{MRT_ERR_INVALID, "null render args"};
-  if (!d_rgb || !d_b || !d_mom || !d_smp) throw ApiError{MRT_ERR_INVALID, "null accumulation buffer"};
+// mrt_render_adaptive(_device): a frame's checks and the rule's own (a is not
+// null), then an empty report. The shard's tiles: none (an empty frame) where
+// the render has nothing to add.
+AdaptFrame check_adaptive(mrt_ctx* c, const mrt_render_args* a, const mrt_adaptive_params* prm,
+                          mrt_adaptive_report* report) {
   if (const char* why = adapt_render_error(prm, a->spp_begin, a->spp_count, a->flags))
     throw ApiError{MRT_ERR_INVALID, why};
-  check_render_args(c, a);
+  check_render_args(c, a);  // before the frame's size is trusted
   check_render_flags(c, a);
-  const uint32_t sc = a->shard_count ? a->shard_count : 1;
-  const AdaptFrame f = adaptive_frame(c, a->width, a->height, a->shard_index, sc);
+  const AdaptFrame f = adaptive_frame(c, a->width, a->height, a->shard_index, a->shard_count ? a->shard_count : 1);
   if (report) *report = mrt_adaptive_report{};
-  const uint32_t cap = a->spp_count;
-  if (cap == 0 || a->max_depth == 0 || f.n_tiles == 0) return;  // nothing to add
-  auto pl = pixlist(c, a->width, a->height, a->shard_index, sc);
-  const uint32_t n_shard = pl.second;
+  return nothing_to_add(a->spp_count, a->max_depth, f.n_tiles) ? AdaptFrame{} : f;
+}
+
+// The rounds of the adaptive rule around the wavefront loop (massrt.h states
+// the rule, host/adaptive.h its arithmetic). Round r is one render_wavefront
+// over the open tiles' pixel list with the round's sample base and the
+// moment-carrying accumulate: plan_buffers, the queues and the drain are a
+// frame's. Behind it on `st` the open tiles are evaluated (k_adaptive_tiles)
+// and the survivors' pixels compacted into the next list (adaptive_compact),
+// whose length the host waits for: one word per round. So the call returns
+// when its last kernel has ended.
+void run_adaptive(mrt_ctx* c, const mrt_render_args* a, const mrt_adaptive_params* prm, const AdaptFrame& f,
+                  const Accum& acc, mrt_adaptive_report* report, hipStream_t st) {
+  const auto pl = pixlist(c, a->width, a->height, a->shard_index, f.sc);
+  const uint32_t cap = a->spp_count, n_shard = pl.second;
   adaptive_scratch(c, f.n_tiles, n_shard);
   HIP_CHECK(hipMemsetAsync(c->ad_open.p, 1, f.n_tiles, st));  // every tile starts in the running
   const float tau2 = adapt_tau2(prm->threshold);
@@ -1036,12 +1035,11 @@ static void render_adaptive_device(mrt_ctx* c, const mrt_render_args* a, const m
       mrt_render_args ra = *a;
       ra.spp_begin = a->spp_begin + done;
       ra.spp_count = cnt;
-      render_wavefront(c, &ra, list, n_pix, first_chunk(cnt, c->tun.results_max, n_pix), ViewTable{}, RayTable{},
-                       d_rgb, d_b, st, Accum{d_mom, d_smp});
+      render_wavefront(c, &ra, list, n_pix, c->cam, acc, st);
       samples += (uint64_t)n_pix * cnt;
       done += cnt;
     }
-    adaptive_evaluate(f, d_mom, d_smp, tau2, prm->floor, c->ad_open.p, true, nullptr, st);
+    adaptive_evaluate(f, acc.moments, acc.samples, tau2, prm->floor, c->ad_open.p, true, nullptr, st);
     uint32_t* next = c->ad_list[round & 1].p;
     w = adaptive_compact(c, f, next, n_shard, round, st);
     list = next;
@@ -1051,6 +1049,34 @@ static void render_adaptive_device(mrt_ctx* c, const mrt_render_args* a, const m
   mark_ctx_busy(c, st);
   if (report) *report = mrt_adaptive_report{round + 1, done, f.n_tiles, w.tiles, samples};
 }
+
+// The host forms' staging: the caller's accumulation buffers of n pixels or
+// rays pass through the context's own on c->stream.
+struct Staging {
+  mrt_ctx* c;
+  size_t n;
+  Accum host;
+  // one buffer, host to device (in) or back: its device pointer, null for one the caller does not have
+  template <typename T>
+  T* pass(DevBuf<T>& d, T* h, size_t count, bool in) {
+    if (!h) return nullptr;
+    if (in) HIP_CHECK(d.reserve(count));
+    HIP_CHECK(in ? hipMemcpyAsync(d.p, h, count * sizeof(T), hipMemcpyHostToDevice, c->stream)
+                 : hipMemcpyAsync(h, d.p, count * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+    return d.p;
+  }
+  Accum all(bool in) {
+    return Accum{pass(c->d_acc_rgb, host.rgb, 3 * n, in), pass(c->d_acc_b, host.bounces, n, in),
+                 pass(c->d_acc_mom, host.moments, 2 * n, in), pass(c->d_acc_n, host.samples, n, in)};
+  }
+  Accum in() { return all(true); }  // the buffers on the device
+  void out() {
+    all(false);
+    HIP_CHECK(hipStreamSynchronize(c->stream));
+  }
+};
+
+}  // namespace
 
 // Kernel timing of renders flagged MRT_RENDER_TIME_KERNELS, resolved when the
 // stats are read (a timed render does not wait for its queue set's drain).
@@ -1085,7 +1111,8 @@ int mrt_render_device(mrt_ctx* c, const mrt_render_args* a, float* d_rgb, uint32
   MRT_DEV0(c, mrt_render_device(c, a, d_rgb, d_b, stream));
   return guarded(c, [&] {
     if (!d_rgb || !d_b) throw ApiError{MRT_ERR_INVALID, "null accumulation buffer"};
-    render_device(c, a, d_rgb, d_b, (hipStream_t)stream);  // NULL: the null stream
+    const Work w = check_render(c, a);
+    if (w.second) run_render(c, a, w, {d_rgb, d_b}, (hipStream_t)stream);  // NULL: the null stream
   });
 }
 
@@ -1093,17 +1120,11 @@ int mrt_render(mrt_ctx* c, const mrt_render_args* a, float* rgb, uint32_t* bounc
   if (c && c->multi) return multi_render(c->multi, a, rgb, bounces, c->err);
   return guarded(c, [&] {
     if (!a || !rgb || !bounces) throw ApiError{MRT_ERR_INVALID, "null argument"};
-    size_t np = (size_t)a->width * a->height;
-    HIP_CHECK(c->d_acc_rgb.reserve(np * 3));
-    HIP_CHECK(c->d_acc_b.reserve(np));
-    float* d_rgb = c->d_acc_rgb.p;
-    uint32_t* d_b = c->d_acc_b.p;
-    HIP_CHECK(hipMemcpyAsync(d_rgb, rgb, np * 12, hipMemcpyHostToDevice, c->stream));
-    HIP_CHECK(hipMemcpyAsync(d_b, bounces, np * 4, hipMemcpyHostToDevice, c->stream));
-    render_device(c, a, d_rgb, d_b, c->stream);
-    HIP_CHECK(hipMemcpyAsync(rgb, d_rgb, np * 12, hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipMemcpyAsync(bounces, d_b, np * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
+    const Work w = check_render(c, a);
+    if (!w.second) return;  // nothing to add: the buffers stay as they are
+    Staging s{c, (size_t)a->width * a->height, {rgb, bounces}};
+    run_render(c, a, w, s.in(), c->stream);
+    s.out();
   });
 }
 
@@ -1112,7 +1133,8 @@ int mrt_render_views_device(mrt_ctx* c, const mrt_render_args* a, const mrt_view
   MRT_DEV0(c, mrt_render_views_device(c, a, views, n_views, d_rgb, d_b, stream));
   return guarded(c, [&] {
     if (!d_rgb || !d_b) throw ApiError{MRT_ERR_INVALID, "null accumulation buffer"};
-    render_views_device(c, a, views, n_views, d_rgb, d_b, (hipStream_t)stream);  // NULL: the null stream
+    const Work w = check_views(c, a, views, n_views);
+    if (w.second) run_views(c, a, w, views, n_views, {d_rgb, d_b}, (hipStream_t)stream);  // NULL: the null stream
   });
 }
 
@@ -1121,20 +1143,11 @@ int mrt_render_views(mrt_ctx* c, const mrt_render_args* a, const mrt_view* views
   MRT_DEV0(c, mrt_render_views(c, a, views, n_views, rgb, bounces));
   return guarded(c, [&] {
     if (!a || !rgb || !bounces) throw ApiError{MRT_ERR_INVALID, "null argument"};
-    if (!views || n_views == 0) throw ApiError{MRT_ERR_INVALID, "mrt_render_views: no views"};
-    if (!views_fit(n_views, a->width, a->height))
-      throw ApiError{MRT_ERR_INVALID, "mrt_render_views: n_views * width * height must be below 2^32"};
-    const size_t np = (size_t)n_views * a->width * a->height;  // the views' frames, one behind the other
-    HIP_CHECK(c->d_acc_rgb.reserve(np * 3));
-    HIP_CHECK(c->d_acc_b.reserve(np));
-    float* d_rgb = c->d_acc_rgb.p;
-    uint32_t* d_b = c->d_acc_b.p;
-    HIP_CHECK(hipMemcpyAsync(d_rgb, rgb, np * 12, hipMemcpyHostToDevice, c->stream));
-    HIP_CHECK(hipMemcpyAsync(d_b, bounces, np * 4, hipMemcpyHostToDevice, c->stream));
-    render_views_device(c, a, views, n_views, d_rgb, d_b, c->stream);
-    HIP_CHECK(hipMemcpyAsync(rgb, d_rgb, np * 12, hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipMemcpyAsync(bounces, d_b, np * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
+    const Work w = check_views(c, a, views, n_views);
+    if (!w.second) return;
+    Staging s{c, (size_t)n_views * a->width * a->height, {rgb, bounces}};  // the views' frames, one behind the other
+    run_views(c, a, w, views, n_views, s.in(), c->stream);
+    s.out();
   });
 }
 
@@ -1144,9 +1157,9 @@ int mrt_render_rays_device(mrt_ctx* c, const mrt_path_ray* d_rays, uint32_t n_ra
   MRT_DEV0(c, mrt_render_rays_device(c, d_rays, n_rays, seed, spp_begin, spp_count, max_depth, flags, d_rgb, d_b,
                                      stream));
   return guarded(c, [&] {
-    check_rays_args(c, d_rays, n_rays, spp_begin, spp_count, flags, d_rgb, d_b, false);
-    render_rays_device(c, d_rays, n_rays, seed, spp_begin, spp_count, max_depth, flags, d_rgb, d_b,
-                       (hipStream_t)stream);  // NULL: the null stream
+    if (check_rays(c, d_rays, n_rays, spp_begin, spp_count, max_depth, flags, d_rgb, d_b, false))
+      run_rays(c, d_rays, n_rays, seed, spp_begin, spp_count, max_depth, flags, {d_rgb, d_b},
+               (hipStream_t)stream);  // NULL: the null stream
   });
 }
 
@@ -1155,8 +1168,10 @@ int mrt_render_adaptive_device(mrt_ctx* c, const mrt_render_args* a, const mrt_a
                                void* stream) {
   MRT_DEV0(c, mrt_render_adaptive_device(c, a, params, d_rgb, d_b, d_moments, d_samples, report, stream));
   return guarded(c, [&] {
-    render_adaptive_device(c, a, params, d_rgb, d_b, d_moments, d_samples, report,
-                           (hipStream_t)stream);  // NULL: the null stream
+    if (!a) throw ApiError{MRT_ERR_INVALID, "null render args"};
+    if (!d_rgb || !d_b || !d_moments || !d_samples) throw ApiError{MRT_ERR_INVALID, "null accumulation buffer"};
+    const AdaptFrame f = check_adaptive(c, a, params, report);
+    if (f.n_tiles) run_adaptive(c, a, params, f, {d_rgb, d_b, d_moments, d_samples}, report, (hipStream_t)stream);
   });
 }
 
@@ -1165,26 +1180,11 @@ int mrt_render_adaptive(mrt_ctx* c, const mrt_render_args* a, const mrt_adaptive
   MRT_DEV0(c, mrt_render_adaptive(c, a, params, rgb, bounces, moments, samples, report));
   return guarded(c, [&] {
     if (!a || !rgb || !bounces || !moments || !samples) throw ApiError{MRT_ERR_INVALID, "null argument"};
-    if (const char* why = adapt_render_error(params, a->spp_begin, a->spp_count, a->flags))
-      throw ApiError{MRT_ERR_INVALID, why};
-    check_render_args(c, a);  // before the frame's size is trusted
-    const size_t np = (size_t)a->width * a->height;
-    HIP_CHECK(c->d_acc_rgb.reserve(np * 3));
-    HIP_CHECK(c->d_acc_b.reserve(np));
-    HIP_CHECK(c->d_acc_mom.reserve(np * 2));
-    HIP_CHECK(c->d_acc_n.reserve(np));
-    float *d_rgb = c->d_acc_rgb.p, *d_mom = c->d_acc_mom.p;
-    uint32_t *d_b = c->d_acc_b.p, *d_n = c->d_acc_n.p;
-    HIP_CHECK(hipMemcpyAsync(d_rgb, rgb, np * 12, hipMemcpyHostToDevice, c->stream));
-    HIP_CHECK(hipMemcpyAsync(d_b, bounces, np * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_CHECK(hipMemcpyAsync(d_mom, moments, np * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_CHECK(hipMemcpyAsync(d_n, samples, np * 4, hipMemcpyHostToDevice, c->stream));
-    render_adaptive_device(c, a, params, d_rgb, d_b, d_mom, d_n, report, c->stream);
-    HIP_CHECK(hipMemcpyAsync(rgb, d_rgb, np * 12, hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipMemcpyAsync(bounces, d_b, np * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipMemcpyAsync(moments, d_mom, np * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipMemcpyAsync(samples, d_n, np * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
+    const AdaptFrame f = check_adaptive(c, a, params, report);
+    if (!f.n_tiles) return;
+    Staging s{c, (size_t)a->width * a->height, {rgb, bounces, moments, samples}};
+    run_adaptive(c, a, params, f, s.in(), report, c->stream);
+    s.out();
   });
 }
 
@@ -1192,23 +1192,15 @@ int mrt_render_rays(mrt_ctx* c, const mrt_path_ray* rays, uint32_t n_rays, uint6
                     uint32_t spp_count, uint32_t max_depth, uint32_t flags, float* rgb, uint32_t* bounces) {
   MRT_DEV0(c, mrt_render_rays(c, rays, n_rays, seed, spp_begin, spp_count, max_depth, flags, rgb, bounces));
   return guarded(c, [&] {
-    check_rays_args(c, rays, n_rays, spp_begin, spp_count, flags, rgb, bounces, true);
-    if (spp_count == 0 || max_depth == 0) return;  // nothing to add: the buffers stay as they are
-    const size_t n = n_rays;
+    if (!check_rays(c, rays, n_rays, spp_begin, spp_count, max_depth, flags, rgb, bounces, true)) return;
     // the table goes into the context's own buffer; the last host-form call's
     // kernels, its only readers, ended before that call returned
-    HIP_CHECK(c->rays_d.reserve(n));
-    HIP_CHECK(c->d_acc_rgb.reserve(n * 3));
-    HIP_CHECK(c->d_acc_b.reserve(n));
-    float* d_rgb = c->d_acc_rgb.p;
-    uint32_t* d_b = c->d_acc_b.p;
-    HIP_CHECK(hipMemcpyAsync(c->rays_d.p, rays, n * sizeof(mrt_path_ray), hipMemcpyHostToDevice, c->stream));
-    HIP_CHECK(hipMemcpyAsync(d_rgb, rgb, n * 12, hipMemcpyHostToDevice, c->stream));
-    HIP_CHECK(hipMemcpyAsync(d_b, bounces, n * 4, hipMemcpyHostToDevice, c->stream));
-    render_rays_device(c, c->rays_d.p, n_rays, seed, spp_begin, spp_count, max_depth, flags, d_rgb, d_b, c->stream);
-    HIP_CHECK(hipMemcpyAsync(rgb, d_rgb, n * 12, hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipMemcpyAsync(bounces, d_b, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(hipStreamSynchronize(c->stream));
+    HIP_CHECK(c->rays_d.reserve(n_rays));
+    HIP_CHECK(hipMemcpyAsync(c->rays_d.p, rays, (size_t)n_rays * sizeof(mrt_path_ray), hipMemcpyHostToDevice,
+                             c->stream));
+    Staging s{c, n_rays, {rgb, bounces}};
+    run_rays(c, c->rays_d.p, n_rays, seed, spp_begin, spp_count, max_depth, flags, s.in(), c->stream);
+    s.out();
   });
 }
 

@@ -185,6 +185,14 @@ inline bool samples_fit(uint32_t spp_begin, uint32_t spp_count) {
   return (uint64_t)spp_begin + spp_count <= 0xFFFFFFFFull;
 }
 
+// A render of spp_count samples of depth max_depth over a list of n pixels or
+// rays has nothing to add when any of the three is 0 (trace(ray, 0) returns
+// (0, 0) for every sample): the buffers stay as they are, and nothing is
+// planned or enqueued for it.
+inline bool nothing_to_add(uint32_t spp_count, uint32_t max_depth, uint32_t n) {
+  return spp_count == 0 || max_depth == 0 || n == 0;
+}
+
 // ---- the fork ---------------------------------------------------------------
 
 // Queue k's share of a chunk's first n0 paths over K queues (<= ceil(P / K),

@@ -195,7 +195,7 @@ def cornell(golden_dir):
 
 
 def test_refill(rctx, grid):
-    """92,160 entries against the smallest pool (65,536 paths): the rest can only come from k_refill_rays."""
+    """92,160 entries against the smallest pool (65,536 paths): the rest can only come from k_refill<RayTable>."""
     w, h, depth = 480, 192, 8
     walk = rctx.get_option("traversal")
     c = massrt.Context(0, options={"traversal": walk, "pool_paths": 65536})

@@ -112,7 +112,7 @@ def test_equals_separate_renders(ctx, grid):
 # pool_paths 65536 is the smallest pool. The first case is 8 chunks of 2 spp
 # (the slab of 2^14 samples against 6 x 960 list pixels; sample_base advances),
 # each of 11,520 work items; the second is one chunk of 92,160 work items,
-# more than the pool, so k_refill_views generates the rest
+# more than the pool, so k_refill<ViewTable> generates the rest
 @pytest.mark.parametrize("finish", [0, None], ids=["finish0", "finish_default"])
 @pytest.mark.parametrize("results_log2", [14, None], ids=["chunks", "refill"])
 def test_refill_chunks_shards(ctx, grid, results_log2, finish):

@@ -164,3 +164,13 @@ def test_status_rule(check):
         assert all(r[7] == "go_on" for r in steps[:-1])  # a sequence ends with its queue
         ends.add(steps[-1][7])
     assert ends == {"hand_off", "finished", "shade_short"}
+
+
+def test_nothing_to_add_is_any_zero_factor(check):
+    """A render adds nothing exactly when it has no samples, no depth or no list entries: the one rule every entry
+    point asks before it plans or enqueues anything."""
+    rows = [tuple(int(x) for x in r) for r in check("nothing")]
+    vals = (0, 1, 7, 2 ** 32 - 1)
+    assert {r[:3] for r in rows} == {(s, d, n) for s in vals for d in vals for n in vals} and len(rows) == 64
+    for spp, depth, n, nothing in rows:
+        assert nothing == (1 if 0 in (spp, depth, n) else 0), (spp, depth, n)

@@ -2,8 +2,8 @@
 (csrc/host/loop.h through tools/views_check.cpp): the view list is the shard's
 list once per view with v W H added, every entry splits back to its (view,
 pixel), the shards of a batch cover every pixel of every view once, and the
-2^32 limit on n_views W H is exact. render.hip builds its lists, and the view
-variants of k_generate / k_refill split their entries, with these functions;
+2^32 limit on n_views W H is exact. render.hip builds its lists, and
+k_generate<ViewTable> / k_refill<ViewTable> split their entries, with these functions;
 on the GPU whole renders see them (tests/test_gpu_views.py)."""
 import shutil
 import subprocess

@@ -19,6 +19,9 @@
 //     on_status, a sequence ending where its queue does: "seq G finish_paths
 //     active0 active1 shade_short work step bound exhausted finished" (step:
 //     go_on, hand_off, finished or shade_short; bound -1: unbounded).
+//   loop_check nothing
+//     nothing_to_add over 0, 1, 7 and 2^32 - 1 in each place: "spp_count
+//     max_depth n 0|1".
 #include <stdio.h>
 #include <string.h>
 
@@ -137,11 +140,20 @@ static int status() {
   return 0;
 }
 
+static int nothing() {
+  const uint32_t vals[] = {0u, 1u, 7u, 0xFFFFFFFFu};
+  for (uint32_t spp : vals)
+    for (uint32_t depth : vals)
+      for (uint32_t n : vals) printf("%u %u %u %d\n", spp, depth, n, nothing_to_add(spp, depth, n) ? 1 : 0);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   const char* mode = argc > 1 ? argv[1] : "";
+  if (!strcmp(mode, "nothing")) return nothing();
   if (!strcmp(mode, "refill")) return refill();
   if (!strcmp(mode, "sizes")) return sizes();
   if (!strcmp(mode, "share")) return share();
   if (!strcmp(mode, "status")) return status();
-  return printf("error: expected refill, sizes, share or status\n"), 2;
+  return printf("error: expected refill, sizes, share, status or nothing\n"), 2;
 }
