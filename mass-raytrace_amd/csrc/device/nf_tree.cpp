@@ -450,6 +450,11 @@ struct Builder {
         const TriBound tbd = tri_bound(ab, ac);
         if (tb) grow_bound(*tb, tbd);
         if (tbd.a1 > 0) gen_extent.push_back(std::max(b.mx[0] - b.mn[0], std::max(b.mx[1] - b.mn[1], b.mx[2] - b.mn[2])));
+        if (tbd.a1 > 0) {  // counted for the host checks (tools/slab_check's bound line)
+          bool planar = false;
+          for (int k = 0; k < 3; ++k) planar = planar || (ab[k] == 0.0f && ac[k] == 0.0f);
+          ++(planar ? s.nf_generic_planar : s.nf_generic);
+        }
         pad_box(b, 0.0f);
         pad_abs(b, tbd.pad);
         break;
@@ -655,6 +660,7 @@ struct Builder {
   bool run() {
     s.nf_ok = false;
     s.nf_first_slot = n_slots();
+    s.nf_generic = s.nf_generic_planar = 0;
     if (s.trav_rng) return (s.nf_note = "the traversal draws random numbers (Volume, Mix alpha)", true);
     if (s.nf_build == kNfBuildNever) return (s.nf_note = "not built (option traversal = REFERENCE at upload)", true);
     if (s.nf_build == kNfBuildAuto && auto_declines())
@@ -726,6 +732,7 @@ struct Builder {
     uint32_t n_world_inst = 0;
     for (uint32_t r : world_objs) n_world_inst += kind(r) == KIND_INST;
     const bool few = n_world_inst <= kNfWildFew;
+    bool flat_sphere = false;  // a sphere whose reference parent box is flat along an axis
     for (uint32_t r : world_objs) {
       const uint32_t kd = kind(r);
       TriBound tb;
@@ -753,6 +760,17 @@ struct Builder {
         Box sb;
         for (int k = 0; k < 3; ++k) sb.mn[k] = f_down(c[k] - rad), sb.mx[k] = f_up(c[k] + rad);
         sph_box.grow(sb);
+        // nf_finish (walk_nf.h) lets the winner's reference parent box stand for every box above it, as
+        // they are nested. A flat parent box (mn_k == mx_k: a sphere smaller than half an ulp of its centre,
+        // alone in its node) breaks that for a ray in its plane with d_k = 0: both of its quotients are 0/0
+        // and min/max pass them over, while a box above with one plane there has 0/0 and an infinity, and
+        // the reference misses it. A sphere can be hit by such a ray (a planar triangle cannot: det = 0).
+        const uint32_t par = s.vnf_leaf[2 * (size_t)vnf_slot(r)];
+        if (par != kNoParent) {
+          float mn[3], mx[3];
+          rec::box_bounds(ws(), par, mn, mx);
+          for (int k = 0; k < 3; ++k) flat_sphere = flat_sphere || mn[k] == mx[k];
+        }
       }
       if (kd == KIND_INST) {
         auto it = region_of.find(rec::blas_begin(ws(), r));
@@ -781,6 +799,7 @@ struct Builder {
     }
     aw0 = std::max(aw0, world_tri.a0), aw1 = std::max(aw1, world_tri.a1);
     if (r_min < 0x1p-60) return (s.nf_note = "a sphere too small for the walk's rounding bound", true);
+    if (flat_sphere) return (s.nf_note = "a sphere in a flat reference box (a ray in its plane meets a 0/0 slab)", true);
     if (!(orad <= kNfObjRadMax)) return (s.nf_note = "an instanced mesh outside the rounding bound's domain (2^12)", true);
     // The world tree holds the other items only: no forced path, and its
     // boxes do not span the wild items' boxes. The wild items get a tree of

@@ -62,6 +62,9 @@ struct HostScene {
   uint32_t nf_wild = 0;  // instances the world margin does not cover: never culled
   uint32_t nf_wild_root = 0;  // their own tree's root record, walked after the world tree (0: none, or it is nf_world)
   uint32_t nf_cones = 0;  // NF nodes carrying a normal cone (nf_bound.h nf_cone_rg)
+  // triangles under the generic bound (nf_tree.cpp tri_bound): those off every coordinate plane, and those on
+  // one that left the coordinate-plane bound by one of its exits (degenerate, beta < 0.5, kappa too large)
+  uint32_t nf_generic = 0, nf_generic_planar = 0;
   // tools/slab_check: set before building to keep every leaf object's NF box
   // (6 floats per vnf_leaf slot: mn xyz, mx xyz) and which instances are wild
   bool keep_nf_boxes = false;

@@ -129,6 +129,11 @@ MRT_HD bool ref_box_hits(const TravIn& in, uint32_t rec, const TRay& r, float t)
 // BoundingBox::hit is monotone in t_max, so B passing at tau suffices; the
 // reference's boxes are nested, so the winner's world parent (world ray) and,
 // inside a BLAS, its BLAS parent (that space's ray) stand for all of them.
+// (Nesting carries over to BoundingBox::hit unless the parent box is flat
+// along an axis k and the ray lies in that plane with d_k = 0: 0/0 on both of
+// its planes, which min/max pass over, but 0/0 and an infinity on a box above
+// with one plane there. Only a sphere can be hit by such a ray; nf_tree.cpp
+// builds no trees for a scene with a sphere in a flat reference box.)
 // Yes: the ray is done (its record set to END for k_trace's box-run ballot).
 // No: the reference's walk from the start (kExactMode).
 template <bool COUNT>

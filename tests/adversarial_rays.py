@@ -9,7 +9,9 @@ walk can go wrong without ordinary rays noticing: zero and subnormal direction
 components, origins on box planes (0/0 in the slab test), rays through box
 corners and along shared triangle edges, directions of 2^-120 to 2^100,
 origins up to 1e38 from the scene (where the reference's own sphere arithmetic
-overflows and accepts a hit with t = NaN), NaN and infinite values.
+overflows and accepts a hit with t = NaN), NaN and infinite values, rays
+grazing a triangle's plane and passing a sphere at nearly its radius. short()
+gives every family again with directions of 2^k.
 
 The custom worlds the GPU tests walk (random_world is tests/test_bvh.py's) are
 built here too, so that their rays come from the same desc() the walk sees."""
@@ -299,21 +301,93 @@ def zero_d(g, n, seed):
     return r
 
 
+def _perpendicular(w):
+    """Unit vectors perpendicular to the unit vectors w [n, 3] (float64)."""
+    e = np.where((np.abs(w[:, 0]) < 0.9)[:, None], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0])
+    t = np.cross(w, e)
+    return t / np.linalg.norm(t, axis=1, keepdims=True)
+
+
+def graze(g, n, seed):
+    """Through a random point of a triangle (one with a normal) at 10^U(-8, -1.5) rad to its plane, either
+    side, the origin 0.5-20 back along the ray; |d| in 0.5-2. Where Moller-Trumbore's t is least accurate and
+    the reference's |det| >= 1e-6 cut decides (tools/slab_check.cpp `graze`, here from the scene's world-space
+    triangles). Computed in float64 and rounded once."""
+    return graze_with_triangles(g, n, seed)[0]
+
+
+def graze_with_triangles(g, n, seed):
+    """graze()'s rays and each ray's triangle [n, 3, 3] (float64)."""
+    rng = np.random.default_rng(seed)
+    t = g["tris"].astype(np.float64).reshape(-1, 3, 3)
+    nn = np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0])
+    ln = np.linalg.norm(nn, axis=1)
+    ok = np.flatnonzero(ln > 0)
+    i = ok[rng.integers(0, len(ok), n)]
+    t, nn = t[i], nn[i] / ln[i, None]
+    b1, b2 = rng.random((n, 1)), rng.random((n, 1))
+    flip = (b1 + b2) > 1
+    b1, b2 = np.where(flip, 1 - b1, b1), np.where(flip, 1 - b2, b2)
+    p = t[:, 0] + b1 * (t[:, 1] - t[:, 0]) + b2 * (t[:, 2] - t[:, 0])
+    t1 = _perpendicular(nn)
+    t2 = np.cross(nn, t1)
+    phi = rng.uniform(0.0, 2.0 * np.pi, (n, 1))
+    th = 10.0 ** rng.uniform(-8.0, -1.5, (n, 1)) * rng.choice([-1.0, 1.0], (n, 1))
+    d = rng.uniform(0.5, 2.0, (n, 1)) * (np.cos(th) * (np.cos(phi) * t1 + np.sin(phi) * t2) + np.sin(th) * nn)
+    back = rng.uniform(0.5, 20.0, (n, 1)) / np.linalg.norm(d, axis=1, keepdims=True)
+    return _rays((p - d * back).astype(np.float32), d), t
+
+
+def family_seed(f, seed=1):
+    """The seed families() passes to family f."""
+    return seed + 1000 * FAMILIES.index(f)
+
+
+def tangent(g, n, seed):
+    """Past a sphere at r (1 +- 10^U(-7, -1)) from its centre, from 1-400 radii before the nearest point;
+    |d| in 0.5-2. Where the sphere test's discriminant cancels (tools/slab_check.cpp `tangent`). Half pass
+    outside. Computed in float64 and rounded once."""
+    rng = np.random.default_rng(seed)
+    s = g["spheres"][rng.integers(0, len(g["spheres"]), n)].astype(np.float64)
+    c, r = s[:, :3], s[:, 3:4]
+    w = _unit(rng, n)
+    off = r * (1.0 + rng.choice([-1.0, 1.0], (n, 1)) * 10.0 ** rng.uniform(-7.0, -1.0, (n, 1)))
+    t1 = _perpendicular(w)
+    back = r * 10.0 ** rng.uniform(0.0, 2.6, (n, 1))
+    d = t1 * rng.uniform(0.5, 2.0, (n, 1))
+    return _rays((c + w * off - t1 * back).astype(np.float32), d)
+
+
 FAMILIES = (axis, on_plane, corners, tri_edges, spheres, scales, tiny_comp, far_big_d, far_unit_d, nan_origin,
-            nan_direction, inf, zero_d)
+            nan_direction, inf, zero_d, graze, tangent)
+# the families aimed at the scene's own boxes and primitives with finite, ordinary-sized values
+GEOMETRIC = ("axis", "on_plane", "corners", "tri_edges", "spheres", "tiny_comp", "graze", "tangent")
 
 
 def families(desc, cam, n=N_FAMILY, seed=1):
     """name -> [n, 6] float32 rays, from the scene's own geometry. A family
-    whose primitives the scene lacks (spheres, tri_edges) is left out."""
+    whose primitives the scene lacks (spheres, tangent; tri_edges, graze) is left out."""
     g = geometry(desc, cam)
     out = {}
     for k, f in enumerate(FAMILIES):
-        if (f is spheres and not len(g["spheres"])) or (f is tri_edges and not len(g["tris"])):
+        if (f in (spheres, tangent) and not len(g["spheres"])) or (f in (tri_edges, graze) and not len(g["tris"])):
             continue
         r = f(g, n, seed + 1000 * k)
         assert r.shape == (n, 6) and r.dtype == np.float32, f.__name__
         out[f.__name__] = r
+    return out
+
+
+def short(name_rays: dict, k: int):
+    """Every family again as `family/short`: the same origins, directions times 2^k. With generic triangles in
+    the scene a ray walks near first only while kw1 |d| <= 2^-8 (nf_bound.h nf_ray_ok), which |d| ~ 1 fails
+    once some |ab||ac| reaches ~3e-3: the short rays are the ones that take the near-first walk there."""
+    out = {}
+    for name, r in name_rays.items():
+        s = r.copy()
+        with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+            s[:, 3:] = np.ldexp(r[:, 3:], k)
+        out[f"{name}/short"] = s
     return out
 
 
@@ -331,8 +405,11 @@ def split(name_rays: dict):
 # that hits nothing would pass any comparison.
 # corners: 48.3% on cube_field and 48.5% on sphere_grid with these generators (many leaf boxes stand on the
 # ground plane, and a ray between two such corners runs in it), so its floor is half of that.
+# graze: 95.5 / 66.5 / 99.5% on cornell / sphere_grid / cube_field and 71.2% or more on adversarial_worlds.py's
+# worlds; tangent (half of its rays pass outside their sphere by construction, and may hit something else):
+# 99.5 / 99.3 / 57.0% and 69.0% or more. Each floor is half of the smallest share.
 HIT_FLOOR = {"nan_origin": 0.25, "tri_edges": 0.5, "spheres": 0.5, "corners": 0.25, "axis": 0.2, "on_plane": 0.2,
-             "tiny_comp": 0.2}
+             "tiny_comp": 0.2, "graze": 0.33, "tangent": 0.28}
 
 
 def is_nan_t(hits):
@@ -347,6 +424,10 @@ def check_floors(want: dict, overflow: bool):
         if name in want:
             share = float((want[name][:, 0] != 0).mean())
             assert share >= floor, f"{name}: the oracle hits {share:.1%} of the rays, under {floor:.0%}"
+    for name in GEOMETRIC:  # short(): the same rays with t_min = 0.001 so much nearer the origin
+        if f"{name}/short" in want:
+            share = float((want[f"{name}/short"][:, 0] != 0).mean())
+            assert share >= 0.2, f"{name}/short: the oracle hits {share:.1%} of the rays, under 20%"
     n = len(want["far_unit_d"])
     far = blocks(FAR_UNIT_K, n) >= 20
     share = float((want["far_unit_d"][far, 0] != 0).mean())

@@ -5,8 +5,6 @@ successor explicit) find the same closest hits, t bits included, after the
 same number of box tests; the early slab decision stays exact
 (tools/slab_check.cpp, which runs k_trace's own walk code, compiled for the
 host, one ray at a time); and both walks' closest hits equal the oracle's."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -15,21 +13,9 @@ import pytest
 import adversarial_rays
 import massrt
 import oracle
-from conftest import GOLDEN, REPO
+from conftest import GOLDEN
 from ray_gen import camera_rays, random_rays
-
-
-@pytest.fixture(scope="module")
-def slab_check(tmp_path_factory):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")  # as the Makefile finds it
-    if not shutil.which(hipcc):
-        pytest.skip("hipcc missing")
-    exe = tmp_path_factory.mktemp("slab") / "slab_check"
-    lib = REPO / "mass-raytrace_amd" / "massrt"
-    subprocess.run([hipcc, "--offload-host-only", "-x", "hip", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
-                    "-o", str(exe), str(REPO / "tools" / "slab_check.cpp"),
-                    f"-L{lib}", "-lmassrt", f"-Wl,-rpath,{lib}"], check=True)
-    return exe
+from slab_tool import slab_check  # noqa: F401 (the fixture: tools/slab_check compiled for the host)
 
 
 @pytest.mark.parametrize("scene", ["cornell", "sphere_grid", "cube_field"])

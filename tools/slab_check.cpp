@@ -22,6 +22,12 @@
 //       n x 6 float32 rays in, n x 4 uint32 out in mrt_trace_rays' layout (k_rays_in -> walk -> k_rays_out)
 //   tools/slab_check eve 0 assets stream
 //       element counts and hashes of the stream, its tables and the treelet (stream_mode)
+//   tools/slab_check @world.txt 0 - hits|hits-nf rays.f32 out.u32 [starts.u8]
+//       the scene is the world file's (load_world below; tests/adversarial_worlds.py writes them), built with the
+//       seed the file names; prints the walk's fallbacks and how many rays started on the reference walk, and
+//       with one more path writes a byte per ray: 1, the ray started near first
+//   tools/slab_check @world.txt 0 - bound rays.f32
+//       the double-precision bound checks on the file's rays (the `nf bound:` line)
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -339,46 +345,73 @@ bool same_hit(const Hit& r, const Hit& q) {
   return r.prim == q.prim && r.container == q.container && (r.prim == kRefNone || f2u(r.t) == f2u(q.t));
 }
 
-// `hits` / `hits-nf`: k_rays_in -> walk -> k_rays_out on the host
-template <uint32_t ALPHA>
-int trace_file(const Scene& c, bool nf, const char* rays_path, const char* out_path) {
-  FILE* f = fopen(rays_path, "rb");
-  if (!f) return fprintf(stderr, "cannot read %s\n", rays_path), 1;
-  std::vector<float> rays;
+// n x 6 float32 rays of a file
+bool read_rays(const char* path, std::vector<float>& rays) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return fprintf(stderr, "cannot read %s\n", path), false;
   float buf[6 * 1024];
   for (size_t k; (k = fread(buf, sizeof(float), 6 * 1024, f)) > 0;) rays.insert(rays.end(), buf, buf + k);
   fclose(f);
+  return true;
+}
+
+// `hits` / `hits-nf`: k_rays_in -> walk -> k_rays_out on the host
+// world: the scene is a world file's — the walk's statistics are printed, and
+// starts_path (if any) gets a byte per ray: 1, the ray started near first
+template <uint32_t ALPHA>
+int trace_file(const Scene& c, bool nf, const char* rays_path, const char* out_path, const char* name, bool world,
+               const char* starts_path) {
+  std::vector<float> rays;
+  if (!read_rays(rays_path, rays)) return 1;
   const size_t n = rays.size() / 6;
   std::vector<uint32_t> out(4 * n);
+  std::vector<uint8_t> near_first(n, 0);
   Stats st;
   uint64_t fb = 0, sr = 0;
   for (size_t i = 0; i < n; ++i) {
     const float* r = &rays[6 * i];
     const V o{r[0], r[1], r[2]}, d{r[3], r[4], r[5]};
+    const uint64_t sr0 = sr;
     const Hit h = nf ? walk_nf<ALPHA>(c, o, d, st, fb, sr) : walk_ref<ALPHA>(c, o, d);
+    near_first[i] = nf && sr == sr0;
     const bool hit = h.prim != kRefNone;
     out[4 * i] = h.prim;
     out[4 * i + 1] = h.container;
     out[4 * i + 2] = hit ? f2u(h.t) : 0u;
     out[4 * i + 3] = hit && resolve_hit(c.S, o, d, h).front_face ? 1u : 0u;
   }
-  f = fopen(out_path, "wb");
+  FILE* f = fopen(out_path, "wb");
   if (!f || fwrite(out.data(), 4, out.size(), f) != out.size()) return fprintf(stderr, "cannot write %s\n", out_path), 1;
   fclose(f);
+  if (world)
+    printf("%-14s %s: %zu rays, fallbacks %llu, starts_ref %llu\n", name, nf ? "hits-nf" : "hits", n,
+           (unsigned long long)fb, (unsigned long long)(nf ? sr : n));
+  if (starts_path) {
+    f = fopen(starts_path, "wb");
+    if (!f || fwrite(near_first.data(), 1, n, f) != n) return fprintf(stderr, "cannot write %s\n", starts_path), 1;
+    fclose(f);
+  }
   return 0;
 }
 
 template <uint32_t ALPHA>
 int run(int argc, char** argv, const mrt_scene_desc& d, const mrt_camera& cam, HostScene& s) {
-  const int n = argc > 2 ? atoi(argv[2]) : 20000;
+  int n = argc > 2 ? atoi(argv[2]) : 20000;
   const char* mode = argc > 4 ? argv[4] : "";
   std::string err;
   const bool hits_nf = !strcmp(mode, "hits-nf");
   if (hits_nf || !strcmp(mode, "hits")) {
     if (argc < 7) return fprintf(stderr, "%s <rays.f32> <out.u32>\n", mode), 1;
     if (hits_nf && !s.nf_ok) return fprintf(stderr, "%s: no near-first trees (%s)\n", argv[1], s.nf_note.c_str()), 1;
-    return trace_file<ALPHA>(Scene(s), hits_nf, argv[5], argv[6]);
+    const bool world = argv[1][0] == '@';
+    return trace_file<ALPHA>(Scene(s), hits_nf, argv[5], argv[6], argv[1], world, world && argc > 7 ? argv[7] : nullptr);
   }
+  // `bound` mode: the double-precision bound checks (check_hit, check_hit_wild, the cones) on the rays of a
+  // file instead of the camera and bounce rays below
+  const bool bound = !strcmp(mode, "bound");
+  std::vector<float> file_rays;
+  if (bound && (argc < 6 || !read_rays(argv[5], file_rays))) return fprintf(stderr, "bound <rays.f32>\n"), 1;
+  if (bound) n = (int)(file_rays.size() / 6);
   // `layout` mode: the same rays through the plain preorder stream (build_host_scene(..., false))
   // and the default layout (BLAS regions with siblings together) must find the
   // same closest hits, t bits included, after the same number of box tests
@@ -386,7 +419,7 @@ int run(int argc, char** argv, const mrt_scene_desc& d, const mrt_camera& cam, H
   const bool layout = !strcmp(mode, "layout");
   // `nf` mode: the verified near-first walk must find the reference's closest
   // hits (primitive, container, t bits) on every ray
-  const bool nf = !strcmp(mode, "nf") || !strcmp(mode, "graze") || !strcmp(mode, "tangent");
+  const bool nf = !strcmp(mode, "nf") || !strcmp(mode, "graze") || !strcmp(mode, "tangent") || bound;
   // `graze` mode: rays nearly parallel to a triangle of the scene (angle
   // 10^U(-8,-1.5) rad to its plane, through a random point of it, from 0.5-60
   // units back; through an instance's transform half the time) — where
@@ -407,8 +440,9 @@ int run(int argc, char** argv, const mrt_scene_desc& d, const mrt_camera& cam, H
   if (nf && s.nf_ok) {
     const NfBound& B = s.nfb;
     printf("%-14s bound: aw0 %.3g aw1 %.3g bw0 %.3g bw1 %.3g kw1 %.3g ko1 %.3g ao0 %.3g ao1 %.3g orad %.3g | world ball r %.3g"
-           " generic r %.3g | spheres r %.3g s51 %.3g s11 %.3g\n", argv[1], B.aw0, B.aw1, B.bw0, B.bw1, B.kw1, B.ko1, B.ao0, B.ao1, B.orad,
-           B.wr, B.gr, B.sr, B.s51, B.s11);
+           " generic r %.3g | spheres r %.3g s51 %.3g s11 %.3g | generic triangles %u off every coordinate plane, %u on one\n",
+           argv[1], B.aw0, B.aw1, B.bw0, B.bw1, B.kw1, B.ko1, B.ao0, B.ao1, B.orad, B.wr, B.gr, B.sr, B.s51, B.s11, s.nf_generic,
+           s.nf_generic_planar);
   }
   if (nf && !s.nf_ok) {
     printf("%-14s nf: no near-first trees (%s)\n", argv[1], s.nf_note.c_str());
@@ -445,7 +479,10 @@ int run(int argc, char** argv, const mrt_scene_desc& d, const mrt_camera& cam, H
   V cam_d{0, 0, -1};
   for (int k = 0; k < n; ++k) {
     V ro, rd;
-    if (tangent) {
+    if (bound) {
+      const float* r = &file_rays[6 * (size_t)k];
+      ro = {r[0], r[1], r[2]}, rd = {r[3], r[4], r[5]};
+    } else if (tangent) {
       if (!d.n_spheres) break;
       const mrt_sphere& sp = d.spheres[std::min<uint32_t>(d.n_spheres - 1, (uint32_t)(u(g) * d.n_spheres))];
       const float rad = fabsf(sp.radius);
@@ -506,7 +543,15 @@ int run(int argc, char** argv, const mrt_scene_desc& d, const mrt_camera& cam, H
     }
     fast += tray_fast(make_tray(ro, rd, scn.S.fast_ok));
     const uint64_t boxes0 = st.boxes;
-    const Hit r = walk_ref<ALPHA>(scn, ro, rd, &st, true);
+    // a file's ray is checked where the bound is claimed: if it starts near first (nf_bound.h nf_ray_ok)
+    bool covered = true;
+    if (bound) {
+      Stats probe;
+      uint64_t fb = 0, sr = 0;
+      walk_nf<ALPHA>(scn, ro, rd, probe, fb, sr);
+      covered = sr == 0;
+    }
+    const Hit r = walk_ref<ALPHA>(scn, ro, rd, &st, covered);
     hits += r.prim != kRefNone;
     if (nf) {
       const uint64_t nb0 = nf_st.boxes;
@@ -623,15 +668,81 @@ int stream_mode(const char* scene, mrt_builder* b, const mrt_scene_desc& d) {
   return 0;
 }
 
+// A world file (tests/adversarial_worlds.py write()): whitespace-separated words, every float a C hex float.
+//   seed <n>                          first: the builder's seed (the reference's tree, and with it its closest
+//                                     hit on a 0/0 slab, depends on the builder's draws)
+//   sphere <c: 3> <r>
+//   tri <abc: 9>
+//   model <add_to_world: 0|1> <n> <n x 9>
+//   instance <model: its number among the file's models> <translation: 3> <rotation: 3> <scale: 3>
+//   camera <vfov> <look_from: 3> <look_at: 3>      (aspect 16:9)
+// One grey Lambertian material for everything, as the Python builders of the same ops use. The tree is built
+// after the last word.
+mrt_builder* load_world(const char* path) {
+  FILE* f = fopen(path, "r");
+  if (!f) return fprintf(stderr, "cannot read %s\n", path), nullptr;
+  char word[32];
+  auto floats = [&](float* v, size_t n) {
+    for (size_t k = 0; k < n; ++k)
+      if (fscanf(f, "%a", &v[k]) != 1) return false;
+    return true;
+  };
+  unsigned long long seed = 0;
+  if (fscanf(f, "%31s %llu", word, &seed) != 2 || strcmp(word, "seed")) return fprintf(stderr, "%s: no seed\n", path), nullptr;
+  mrt_builder* b = nullptr;
+  mrt_builder_new(seed, &b);
+  const uint32_t mat = (uint32_t)mrt_builder_material(b, MRT_MAT_LAMBERTIAN, (uint32_t)mrt_builder_solid(b, 0.5f, 0.5f, 0.5f, 1.0f),
+                                                      0.0f, 0.0f, 0.0f, 0.0f);
+  std::vector<int> models;
+  bool ok = true;
+  while (ok && fscanf(f, "%31s", word) == 1) {
+    float v[10];
+    if (!strcmp(word, "sphere")) {
+      ok = floats(v, 4) && mrt_builder_add_sphere(b, mat, v[0], v[1], v[2], v[3]) == 0;
+    } else if (!strcmp(word, "tri")) {
+      ok = floats(v, 9) && mrt_builder_add_triangle(b, mat, v) == 0;
+    } else if (!strcmp(word, "model")) {
+      unsigned add = 0, n = 0;
+      ok = fscanf(f, "%u %u", &add, &n) == 2 && n > 0 && n < (1u << 20);
+      std::vector<float> tris(ok ? 9 * (size_t)n : 0);
+      ok = ok && floats(tris.data(), tris.size());
+      if (ok) models.push_back(mrt_builder_model(b, mat, 0xFFFFFFFFu, tris.data(), n, 0, (int)add));
+      ok = ok && models.back() >= 0;
+    } else if (!strcmp(word, "instance")) {
+      unsigned m = 0;
+      ok = fscanf(f, "%u", &m) == 1 && m < models.size() && floats(v, 9) &&
+           mrt_builder_add_instance(b, models[m], v, v + 3, v + 6, 0xFFFFFFFFu) == 0;
+    } else if (!strcmp(word, "camera")) {
+      const float up[3] = {0, 1, 0};
+      ok = floats(v, 7);
+      const float e[3] = {v[1] - v[4], v[2] - v[5], v[3] - v[6]};
+      ok = ok && mrt_builder_camera(b, v[0], v + 1, v + 4, up, 16.0f / 9.0f, 0.0f, sqrtf((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2])) == 0;
+    } else {
+      ok = false;
+    }
+  }
+  fclose(f);
+  if (!ok) {
+    fprintf(stderr, "%s: cannot use `%s` (%s)\n", path, word, mrt_builder_last_error());
+    mrt_builder_free(b);
+    return nullptr;
+  }
+  return b;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc < 2) return 1;
   mrt_builder* b = nullptr;
-  mrt_builder_new(1, &b);
-  if (mrt_builder_builtin(b, argv[1], 16.0f / 9.0f, argc > 3 ? argv[3] : "tests/golden") != 0) {
-    printf("%s: %s\n", argv[1], mrt_global_last_error());
-    return 1;
+  if (argv[1][0] == '@') {  // a world file
+    if (!(b = load_world(argv[1] + 1))) return 1;
+  } else {
+    mrt_builder_new(1, &b);
+    if (mrt_builder_builtin(b, argv[1], 16.0f / 9.0f, argc > 3 ? argv[3] : "tests/golden") != 0) {
+      printf("%s: %s\n", argv[1], mrt_global_last_error());
+      return 1;
+    }
   }
   mrt_builder_build_bvh(b);
   mrt_scene_desc d;
